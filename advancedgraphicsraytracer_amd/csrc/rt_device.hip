@@ -136,6 +136,8 @@ inline int hw_queues() {
 
 struct rt_renderer {
     rt_scene *scene = nullptr;
+    int device = 0;             // the scene's device, for rt_renderer_destroy: a caller (Python's
+                                // garbage collector) may have destroyed the scene first
     uint32_t W = 0, H = 0;
     float4 *d_acc = nullptr;
     unsigned long long *d_counters = nullptr;
@@ -2118,6 +2120,7 @@ int rt_renderer_create(rt_scene *s, uint32_t W, uint32_t H, rt_renderer **out) {
     HIP_TRY(hipSetDevice(s->device));
     rt_renderer *r = new rt_renderer();
     r->scene = s;
+    r->device = s->device;
     r->W = W; r->H = H;
     hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&r->d_acc, sizeof(float4) * (size_t)W * H);   // Renderer::Init, renderer.cpp:6-12
@@ -2138,7 +2141,9 @@ int rt_renderer_create(rt_scene *s, uint32_t W, uint32_t H, rt_renderer **out) {
 
 int rt_renderer_destroy(rt_renderer *r) {
     if (!r) return RT_OK;
-    (void)hipSetDevice(r->scene->device);
+    // not r->scene->device: the scene may already be gone, and a freed scene's bytes gave
+    // hipSetDevice an invalid ordinal, which the thread's next hipGetLastError() then reported
+    (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();   // kernels on caller streams may still read the buffers
     (void)hipFree(r->d_acc);
     (void)hipFree(r->d_counters);

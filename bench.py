@@ -9,6 +9,14 @@ resident in HBM before timing; synthetic data = the bundled teapot mesh + the sy
 constant sky.  --config 3 / 4 / 5 select the other BASELINE.json GPU workloads:
 CFG3-sub 4 spp depth 4, mig29 x16 primary + shadow, CFG5-sub 16 spp depth 10.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: scene
+and renderer set-up, the clock ramp, W warm-up steps, N timed steps, the result line.  --full
+adds everything else the benchmark measures, after the timed region: the camera-walk check,
+configs 4 / 3 / 5 (strong_config4, config3, config5), the 1280x720 companion, the CPU baseline
+and, at N > 1, the instrumented per-rank render / gather pass (--no-cpu-baseline, --no-companion,
+--no-strong and --extra-configs trim a --full run).  --dump-outputs DIR writes what the last
+timed step computed (the RGB8 frame and the accumulator) as .npy files.
+
 N > 1 (python -m torch.distributed.run ... bench.py --gpus N): the frame's 8x8 tiles are
 interleaved over the ranks, each rank renders its shard, ONE RCCL gather per frame brings
 the packed tiles to rank 0, which assembles the image.  The exchange is
@@ -215,6 +223,14 @@ def parse():
     ap.add_argument("--ramp-seconds", type=float, default=0.5,
                     help="untimed frames before the warm-up steps until this much wall time has passed: the "
                          "GPU clocks ramp up over ~0.1 s, and 5 warm-up frames are only ~0.5 ms of work")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything else the benchmark "
+                    "measures: camera-walk check, configs 4 / 3 / 5, the 1280x720 companion, the CPU baseline and "
+                    "(N > 1) the instrumented render / gather pass; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last of "
+                    "them computed as DIR/<name>.npy (float32): frame_rgb8 [H, W, 3] and, at N = 1, accumulator "
+                    "[H, W, 4]; a fixed seeded sample of the pixels (pixel_index.npy) when they exceed 64 MB.  At "
+                    "N = 1 the steps after the clock ramp start from a cleared accumulator at frame 0, so equal "
+                    "arguments give equal outputs; at N > 1 only with --ramp-seconds 0")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-companion", action="store_true", help="skip the 1280x720 companion run (profiling runs: "
                     "its frames would share the frame kernel's name in the kernel trace)")
@@ -228,6 +244,8 @@ def parse():
     ap.add_argument("--hw-queues", type=int, default=None, help="GPU_MAX_HW_QUEUES for this run (applied before HIP "
                     "starts; default: 8 for path-traced and N > 1 runs, else the environment's / HIP's default)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     args.scene = args.scene or cfg["scene"]
     args.spp = args.spp or cfg["spp"]
@@ -461,6 +479,33 @@ def extra_config(cfg_no, world, rank, device, dist, stream, summary, backend="nc
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, W, H, frame_rgb8, accumulator=None):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, as float32
+    .npy files under `path`: frame_rgb8 [H, W, 3] (the packed 0x00RRGGBB frame, one channel per
+    column) and accumulator [H, W, 4] (the renderer's running average and its sample count).  Above
+    DUMP_LIMIT_BYTES in all, the same seeded sample of the pixels of both ([n, 3], [n, 4]) and its
+    pixel_index [n] (float64, y * W + x)."""
+    os.makedirs(path, exist_ok=True)
+    px = np.asarray(frame_rgb8).reshape(-1).view(np.uint32)
+    arrays = {"frame_rgb8": np.stack([(px >> 16) & 255, (px >> 8) & 255, px & 255], axis=1).astype(np.float32)}
+    if accumulator is not None:
+        arrays["accumulator"] = np.ascontiguousarray(accumulator, np.float32).reshape(-1, 4)
+    per_pixel = sum(a.shape[1] * 4 for a in arrays.values())
+    room = DUMP_LIMIT_BYTES - 4096   # the .npy headers
+    if W * H * per_pixel > room:
+        keep = np.sort(np.random.default_rng(0).choice(W * H, room // (per_pixel + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["pixel_index"] = keep.astype(np.float64)
+    else:
+        arrays = {k: a.reshape(H, W, -1) for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -518,6 +563,8 @@ def main():
         if sharded is None:
             sharded = ShardedFrame(rend, device=torch.device("cuda", device))
 
+    clear = [False]   # the next N = 1 step clears the accumulator first (the frame's reset flag)
+
     def step(i, events=None):
         with torch.cuda.stream(stream):
             if sharded is not None:
@@ -527,7 +574,8 @@ def main():
                 return
             if events is not None:
                 events[0].record(stream)
-            rend.Tick(frame_out, spp=spp, depth=args.depth, frame=i, stream=sptr)
+            reset, clear[0] = clear[0], False
+            rend.Tick(frame_out, spp=spp, depth=args.depth, frame=i, reset=reset, stream=sptr)
             if events is not None:
                 events[1].record(stream)
 
@@ -570,6 +618,13 @@ def main():
     drain()
     torch.cuda.synchronize(device)
     ramp_frames = nf
+    if sharded is None:
+        # how many frames the ramp's wall time held varies from run to run: the steps after it count
+        # their frames from 0 and the first of them clears the accumulator, so what the last timed
+        # step computes depends on the arguments alone (--dump-outputs).  The renderer's timed
+        # choices are keyed by the frame's size, spp, depth and camera: they carry over.
+        nf = 0
+        clear[0] = True
     for i in range(args.warmup):
         step(nf)
         nf += 1
@@ -601,7 +656,11 @@ def main():
     t1 = time.perf_counter()
     c1 = rend.counters()
     elapsed = t1 - t0
-    if sharded is not None:   # untimed instrumented pass: per-frame render / exposed-gather times
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything below renders further frames
+        dumped = dump_outputs(args.dump_outputs, W, H, (sharded.frame if sharded is not None else frame_out).cpu().numpy(),
+                              rend.accumulator() if sharded is None else None)
+    if sharded is not None and args.full:   # untimed instrumented pass: per-frame render / exposed-gather times
         sharded.set_timing(True)
         for k in range(min(args.steps, 20)):
             step(nf + args.steps + k)
@@ -617,16 +676,17 @@ def main():
     multi = None
     if sharded is not None:
         tm = sharded.timing()
-        if tm is not None:   # this rank's render and exposed gather time per frame (max over ranks)
-            rms, gms, n = tm
-            per = torch.tensor([rms / max(n, 1), gms / max(n, 1)], dtype=torch.float64, device=dev)
-            dist.all_reduce(per, op=dist.ReduceOp.MAX)
+        if tm is not None:
             di = sharded.deal_info()   # the deal this rank's frames actually ran under
             multi = {"exchange": "rt_render_frame_multi (RCCL send/recv to rank 0 from C++, pipelined)",
                      "deal_requested": "balanced (RT_MULTI_BALANCED)" if balanced_deal else "interleaved t % N",
-                     "deal_rank0": {"in_use": "balanced" if di["balanced"] else "interleaved", **di},
-                     "render_ms_per_frame_max_rank": round(per[0].item(), 4),
-                     "gather_ms_per_frame_max_rank": round(per[1].item(), 4)}
+                     "deal_rank0": {"in_use": "balanced" if di["balanced"] else "interleaved", **di}}
+            if args.full:   # this rank's render and exposed gather time per frame (max over ranks)
+                rms, gms, n = tm
+                per = torch.tensor([rms / max(n, 1), gms / max(n, 1)], dtype=torch.float64, device=dev)
+                dist.all_reduce(per, op=dist.ReduceOp.MAX)
+                multi.update(render_ms_per_frame_max_rank=round(per[0].item(), 4),
+                             gather_ms_per_frame_max_rank=round(per[1].item(), 4))
         else:
             multi = {"exchange": f"torch.distributed gather ({backend})"}
             if native_fallback:
@@ -640,7 +700,7 @@ def main():
     in_flight = rend.overlap_depth()
     choices = rend.choices() if args.depth == 1 else None   # the renderer's timed camera-walk / split choices
     walk_check = None
-    if choices is not None and choices["walk"] == 1 and sharded is None:
+    if args.full and choices is not None and choices["walk"] == 1 and sharded is None:
         # untimed: the wave camera walk's counters (lanes re-traced in the reference order, boxes
         # entered through its cull margin) over 10 frames, then 10 frames re-tracing EVERY walked
         # lane in the reference order and counting results that differ (rt_renderer_walk_stats)
@@ -658,7 +718,7 @@ def main():
                       "verify_rays": w2["walked"] - w1["walked"], "verify_mismatch": w2["verify_mismatch"]}
     extras = {}
     default_cfg2 = (args.config, args.scene, W, H, args.spp, args.depth) == (2, "teapotF", 1920, 1080, 1, 1)
-    extra_list = [int(c) for c in args.extra_configs.split(",") if c.strip()] if not args.no_strong else []
+    extra_list = [int(c) for c in args.extra_configs.split(",") if c.strip()] if args.full and not args.no_strong else []
     if default_cfg2 and extra_list:
         if sharded is not None:   # the headline communicator is done (its frames are flushed)
             sharded.close()
@@ -677,7 +737,7 @@ def main():
                 print(f"bench: config {c}: " + (f"{ec['ms_per_frame']} ms per frame, {ec['mrays_s']} Mrays/s"
                                                  if "error" not in ec else ec["error"]), file=sys.stderr, flush=True)
     companion = None
-    if world == 1 and args.depth == 1 and (W, H) == (1920, 1080) and not args.no_companion:   # the metric's other frame size
+    if args.full and world == 1 and args.depth == 1 and (W, H) == (1920, 1080) and not args.no_companion:   # the metric's other frame size
         # the measured renderer is done: free its streams first, so that the companion's
         # frames-in-flight streams get hardware queues of their own (with 8 queues a second
         # renderer beside the first ran config 4's 720p frames at 0.234 instead of 0.168 ms)
@@ -750,7 +810,9 @@ def main():
         if companion:
             line["at_720p"] = companion
         line.update(extras)   # strong_config4, config3, config5 (EXTRA_CONFIGS)
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args, spp)
             except Exception as e:   # the baseline is reported, never the product

@@ -629,34 +629,48 @@ def test_overlapped_primary_shadow_frames_equal_serial(rt, torch, monkeypatch, r
     monkeypatch.setenv("RT_PS_DEPTH", str(depth))
     s1 = rt.Scene.recipe(recipe)
     r0, r1 = rt.Renderer(s0, W, H), rt.Renderer(s1, W, H)
-    plan = [(1, 1, False)] * 320 + [(2, 1, False), (2, 3, False), (1, 1, False), (1, 1, True), (1, 1, False),
-                                    (1, 1, False)]
+    tail = [(2, 1, False), (2, 3, False), (1, 1, False), (1, 1, True), (1, 1, False), (1, 1, False)]
+    # Walk, split order and frames in flight are timed over ~300 frames when every timed group runs
+    # once (1 + 16 + 1, 16 + 1, 8 x 32 + 1 of a deep timing).  A group whose frames the host submitted
+    # slower than the GPU rendered them starts again, at most 4 times (kTuneRestarts) from at most its
+    # last frame: up to 4 x 3 more frames for each of the 8 groups of 4, 4 x 31 for each of the 8
+    # groups of 32 -- 1378 frames at the worst.  The renderer under test (r1) goes first and renders
+    # primary+shadow frames beyond the 320 until its choice is made (never past LIMIT); the serial
+    # renderer then renders the same frames.
+    LIMIT = 1400
     cap = r0.shard_capacity(shards)
     st = torch.cuda.Stream()
-    outs, states, nbuf = [], [], []
+
+    def render(r, f, spp, depth_, reset):
+        if shards == 1:
+            o = torch.zeros(W * H, dtype=torch.int32, device="cuda:0")
+            r.Tick(o, spp=spp, depth=depth_, frame=f, reset=reset, stream=st.cuda_stream)
+        else:
+            o = torch.zeros(cap, dtype=torch.int32, device="cuda:0")
+            r.render_shard(o, 1, shards, spp=spp, depth=depth_, frame=f, reset=reset, stream=st.cuda_stream)
+        return o
+
+    outs, states, nbuf = {}, {}, {}
     with torch.cuda.stream(st):
-        for r in (r0, r1):
-            frames = []
-            for f, (spp, depth_, reset) in enumerate(plan):
-                if shards == 1:
-                    o = torch.zeros(W * H, dtype=torch.int32, device="cuda:0")
-                    r.Tick(o, spp=spp, depth=depth_, frame=f, reset=reset, stream=st.cuda_stream)
-                else:
-                    o = torch.zeros(cap, dtype=torch.int32, device="cuda:0")
-                    r.render_shard(o, 1, shards, spp=spp, depth=depth_, frame=f, reset=reset, stream=st.cuda_stream)
-                frames.append(o)
-                if f == 319:
-                    states.append(r.overlap_depth()[0])
-                    nbuf.append(r.device_bytes()[1])
-            outs.append(frames)
+        n = 320
+        for r in (r1, r0):
+            frames = [render(r, f, 1, 1, False) for f in range(n)]
+            while r is r1 and r.overlap_depth()[0] == -1 and len(frames) < LIMIT:
+                frames.append(render(r, len(frames), 1, 1, False))
+            n = len(frames)
+            states[r] = r.overlap_depth()[0]
+            nbuf[r] = r.device_bytes()[1]
+            frames += [render(r, n + k, *t) for k, t in enumerate(tail)]
+            outs[r] = frames
     torch.cuda.synchronize()
-    # frames in flight each renderer runs after its 320 primary+shadow frames (walk, split order and
-    # frames in flight timed: up to ~300 frames, 32 per frames-in-flight group of a deep timing)
+    print(f"choice made within {n} primary+shadow frames")
+    states, nbuf = [states[r0], states[r1]], [nbuf[r0], nbuf[r1]]
+    # frames in flight each renderer runs after its timed primary+shadow frames
     assert states[0] == 1 and (states[1] == depth if mode == "1" else states[1] in (1, 2, 4, 6)), states
     assert nbuf == [0, 0 if states[1] == 1 else states[1] + 1], (states, nbuf)
-    for f in range(len(plan)):
-        a, b = outs[0][f].cpu().numpy(), outs[1][f].cpu().numpy()
-        assert np.array_equal(a, b), f"frame {f}: {(a != b).sum()} pixels differ"
+    for f in range(n + len(tail)):
+        a, b = outs[r0][f], outs[r1][f]
+        assert torch.equal(a, b), f"frame {f}: {int((a != b).sum())} pixels differ"
     assert np.array_equal(r0.accumulator(), r1.accumulator())
     assert r0.counters() == r1.counters()
 
@@ -996,3 +1010,19 @@ def test_sbvh_scene_matches_plain_oracle_except_ties(rt, oracle, scenes, recipe)
     _, cwobj, _, _ = o.intersect(cam)
     tie_px = set(np.nonzero(cobj != cwobj)[0].tolist())
     assert set(np.nonzero(got != want)[0].tolist()) <= tie_px
+
+
+def test_scene_closed_before_its_renderer_leaves_no_hip_error(rt, torch):
+    """Python's garbage collector finalises a Scene and its Renderer in either order when both sit
+    in a reference cycle (a frame kept by `pytest.raises(...) as e`).  Destroying the renderer
+    after its scene must not touch the freed scene: reading its device there handed hipSetDevice
+    an invalid ordinal, and the thread's next launch check (hipGetLastError) reported it."""
+    g = rt.Scene.recipe("teapotF")
+    r = rt.Renderer(g, 64, 48)
+    r.tick_host(spp=1, depth=1, frame=0)
+    g.close()
+    r.close()
+    g2 = rt.Scene.recipe("teapotF")
+    t, obj, _, _ = g2.IntersectBVH(random_rays(256, 3))   # the launch check reads the thread's last HIP error
+    assert t.shape == (256,) and obj.shape == (256,)
+    g2.close()

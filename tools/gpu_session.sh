@@ -19,8 +19,8 @@ for s in "$@"; do
     case "$s" in
         smoke) step smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
         tests) step gpu_tests 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 240 --timeout-method thread ;;
-        bench) step bench 600 python bench.py --steps 30 --warmup 5 ;;
-        benchdrv) step bench_drv 300 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+        bench) step bench 600 python bench.py --steps 30 --warmup 5 --full ;;
+        benchdrv) step bench_drv 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
         shard)     # per-rank frame times of the N > 1 workloads on one GPU (tools/shard_time.py)
             step shard_mig 300 env GPU_MAX_HW_QUEUES=8 python tools/shard_time.py --scene mig16 --strong --deal interleaved,balanced --out gpurun_out/shard_time.jsonl
             step shard_tp 300 env GPU_MAX_HW_QUEUES=8 python tools/shard_time.py --scene teapotF --deal interleaved,balanced --out gpurun_out/shard_time.jsonl ;;
