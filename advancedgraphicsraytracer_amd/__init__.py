@@ -124,6 +124,9 @@ def lib():
                                 C.POINTER(u32)], C.c_int),
         "rt_bvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, vp, C.POINTER(u32), C.POINTER(SceneInfo)],
                               C.c_int),
+        "rt_bvh_refit_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, vp, u32, C.POINTER(u32)], C.c_int),
+        "rt_scene_update_triangles": ([vp, u32, u32, vp, vp], C.c_int),
+        "rt_scene_update_triangles_host": ([vp, u32, u32, fp], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -306,6 +309,18 @@ def build_bvh_host(prims):
                                    nodes.ctypes.data_as(C.c_void_p),
                                    idx.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(info)))
     return nodes[:info.nodes_used], idx, _info_dict(info)
+
+
+def refit_bvh_host(prims, nodes, idx):
+    """rt_bvh_refit_host: the boxes of a plain tree (nodes [n, 32] uint8, indices) refitted to prims
+    on the host -- what Scene.update_triangles leaves on the device.  Returns the new nodes."""
+    arr = (Prim * len(prims))(*prims)
+    T = _transforms(prims)
+    out = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 32).copy()
+    ix = np.ascontiguousarray(idx, np.uint32)
+    _check(lib().rt_bvh_refit_host(arr, None if T is None else T.ctypes.data_as(C.POINTER(C.c_float)), len(prims),
+                                   out.ctypes.data_as(C.c_void_p), len(out), ix.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out
 
 
 def build_sbvh_host(prims):
@@ -493,6 +508,22 @@ class Scene:
         _check(self.L.rt_scene_copy_bvh(self.h, nodes.ctypes.data_as(C.c_void_p),
                                         idx.ctypes.data_as(C.POINTER(C.c_uint32))))
         return nodes, idx
+
+    def update_triangles(self, first, verts, stream=None):
+        """rt_scene_update_triangles: new vertices for triangle primitives [first, first + count) and an
+        in-place BVH refit.  verts: [count, 9] (or [count, 3, 3]) float32, A, B, C per triangle -- a torch
+        tensor on the scene's device, or a numpy array (staged by the library).  Blocks until the scene
+        is ready; render the next frame with reset=True."""
+        torch = _torch()
+        if isinstance(verts, torch.Tensor) and verts.is_cuda:
+            if verts.device.index != self.device:
+                raise RTError(RT_ERR_INVALID, "update_triangles: vertices on another device than the scene")
+            v = verts.to(dtype=torch.float32).contiguous().reshape(-1, 9)
+            s = stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
+            _check(self.L.rt_scene_update_triangles(self.h, first, v.shape[0], C.c_void_p(v.data_ptr()), C.c_void_p(s)))
+            return
+        v = np.ascontiguousarray(verts.numpy() if isinstance(verts, torch.Tensor) else verts, np.float32).reshape(-1, 9)
+        _check(self.L.rt_scene_update_triangles_host(self.h, first, len(v), _fptr(v)))
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

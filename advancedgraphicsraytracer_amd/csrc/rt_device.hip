@@ -32,6 +32,7 @@
 
 #include "rt_dev_types.h"
 #include "rt_internal.h"
+#include "rt_refit.h"
 
 
 
@@ -118,6 +119,17 @@ struct rt_scene {
     void *d_scratch = nullptr;  // staging for the host-pointer batched calls
     size_t scratch_bytes = 0;
     hipStream_t stream = nullptr;
+    // in-place triangle updates (rt_scene_update_triangles).  Kept from creation: per primitive its
+    // type | sticky << 7 (mark_sticky) and its box (prim_geometry; 6 floats) -- what a refit needs of
+    // the primitives that do not move.  The plan and its device arrays are built by the first update.
+    std::vector<uint8_t> pinfo;
+    std::vector<float> pbox;
+    double sliver_lim = 0.0;        // mark_sticky's sine limit at creation (RT_WALK_STICKY)
+    bool boxes_finite = true;       // every primitive box was finite at creation
+    bool refit_ready = false;
+    RefitPlan plan;
+    void *d_slot_of = nullptr, *d_slot_box = nullptr, *d_list = nullptr, *d_lvl = nullptr, *d_grp = nullptr, *d_flag = nullptr;
+    bool bvh_stale = false;         // the device boxes are newer than bvh.nodes (rt_scene_copy_bvh downloads them)
 };
 
 // renderer streams: up to 8 -- frames in flight of overlapped primary+shadow frames (timed
@@ -414,7 +426,8 @@ void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads};
+    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads,
+                    s->d_slot_of, s->d_slot_box, s->d_list, s->d_lvl, s->d_grp, s->d_flag};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -450,7 +463,7 @@ inline f3 tvec_host(float4 r0, float4 r1, float4 r2, f3 a) {
 // slab miss.  Computed in double on the float vertices.  b.w then holds the walk's cull margin per
 // node: `margin` (SceneView::walk_margin), +inf for a sticky node; the lane traversals never read it.
 void mark_sticky(const Bvh &b, const rt_scene_desc *d, std::vector<float4> &nodes, std::vector<uint8_t> &sticky,
-                 float margin) {
+                 float margin, std::vector<uint8_t> &prim_flag, double &sliver_lim) {
     double lim = std::ldexp(1.0, -8);
     if (const char *e = std::getenv("RT_WALK_STICKY")) lim = std::atoi(e) >= 0 ? 0.0 : std::ldexp(1.0, std::atoi(e));
     bool spheres = true;   // RT_WALK_STICKY_SPHERES=0: A/B only
@@ -471,6 +484,9 @@ void mark_sticky(const Bvh &b, const rt_scene_desc *d, std::vector<float4> &node
         std::sort(len, len + 3);
         return !(area2 >= lim * len[1] * len[2]);   // sine of the smallest angle = 2 area / (two longest edges)
     };
+    sliver_lim = lim;
+    prim_flag.resize(d->num_prims);
+    for (uint32_t i = 0; i < d->num_prims; ++i) prim_flag[i] = prim_sticky(d->prims[i]) ? 1 : 0;
     const uint32_t used = b.nodes_used;
     std::vector<uint32_t> parent(used, ~0u);
     for (uint32_t i = 0; i < used; ++i)
@@ -480,7 +496,7 @@ void mark_sticky(const Bvh &b, const rt_scene_desc *d, std::vector<float4> &node
         const Node &nd = b.nodes[i];
         if (i == 1 || nd.count == 0 || nodes[2 * i + 1].w != 0.0f) continue;
         bool st = false;
-        for (uint32_t k = nd.leftFirst; k < nd.leftFirst + nd.count && !st; ++k) st = prim_sticky(d->prims[b.indices[k]]);
+        for (uint32_t k = nd.leftFirst; k < nd.leftFirst + nd.count && !st; ++k) st = prim_flag[b.indices[k]] != 0;
         for (uint32_t j = i; st && j != ~0u && nodes[2 * j + 1].w == 0.0f; j = parent[j]) nodes[2 * j + 1].w = 1.0f;
     }
     sticky.assign(used, 0);
@@ -592,7 +608,20 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     s->view.walk_margin = 0x1p-12f;
     if (const char *e = std::getenv("RT_WALK_MARGIN"))
         s->view.walk_margin = std::ldexp(1.0f, std::max(-40, std::min(-1, std::atoi(e))));
-    mark_sticky(s->bvh, d, nodes, sticky, s->view.walk_margin);
+    mark_sticky(s->bvh, d, nodes, sticky, s->view.walk_margin, s->pinfo, s->sliver_lim);
+    s->pbox.resize(6 * (size_t)n);
+    for (uint32_t id = 0; id < n; ++id) {
+        PrimX x;
+        PrimGeom g;
+        prim_transform(d->prims[id], d->transforms ? d->transforms + 16 * (size_t)id : nullptr, x);
+        prim_geometry(d->prims[id], x, g);
+        const float bx[6] = {g.bmin.x, g.bmin.y, g.bmin.z, g.bmax.x, g.bmax.y, g.bmax.z};
+        for (int c = 0; c < 6; ++c) {
+            s->pbox[6 * (size_t)id + c] = bx[c];
+            if (!std::isfinite(bx[c])) s->boxes_finite = false;
+        }
+        s->pinfo[id] = (uint8_t)(d->prims[id].type | (s->pinfo[id] ? 0x80 : 0));
+    }
     std::vector<float4> quads;
     uint32_t quad_root = 0;
     {
@@ -1987,11 +2016,127 @@ int rt_scene_set_camera_walk(rt_scene *s, int walk) {
     return RT_OK;
 }
 
-int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices) {
-    if (!s || !nodes || !indices) return fail(RT_ERR_INVALID, "null argument");
+int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
+    if (!cs || !nodes || !indices) return fail(RT_ERR_INVALID, "null argument");
+    rt_scene *s = const_cast<rt_scene *>(cs);
+    if (s->bvh_stale) {   // boxes refitted on the device since the last copy (updates block, so they are settled)
+        HIP_TRY(hipSetDevice(s->device));
+        std::vector<float4> dn(2 * (size_t)s->bvh.nodes_used);
+        HIP_TRY(hipMemcpy(dn.data(), s->d_nodes, sizeof(float4) * dn.size(), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < s->bvh.nodes_used; ++i) {
+            Node &nd = s->bvh.nodes[i];
+            const float4 a = dn[2 * (size_t)i], b = dn[2 * (size_t)i + 1];
+            nd.mn[0] = a.x; nd.mn[1] = a.y; nd.mn[2] = a.z;
+            nd.mx[0] = a.w; nd.mx[1] = b.x; nd.mx[2] = b.y;
+        }
+        s->bvh_stale = false;
+    }
     std::memcpy(nodes, s->bvh.nodes.data(), sizeof(Node) * s->bvh.nodes_used);
     std::memcpy(indices, s->bvh.indices.data(), sizeof(uint32_t) * s->bvh.indices.size());
     return RT_OK;
+}
+
+// the refit plan and its device arrays, on the first update of a scene
+static int ensure_refit(rt_scene *s) {
+    if (s->refit_ready) return RT_OK;
+    const uint32_t n = s->num_prims;
+    if (!build_refit_plan(s->bvh, n, s->plan)) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
+    std::vector<float4> box(2 * (size_t)n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t id = s->bvh.indices[k];
+        const float *b = &s->pbox[6 * (size_t)id];
+        box[2 * (size_t)k] = make_float4(b[0], b[1], b[2], ubits((s->pinfo[id] & 0x80) ? 1u : 0u));
+        box[2 * (size_t)k + 1] = make_float4(b[3], b[4], b[5], 0.0f);
+    }
+    int rc = upload(&s->d_slot_of, s->plan.slot_of);
+    if (rc == RT_OK) rc = upload(&s->d_slot_box, box);
+    if (rc == RT_OK) rc = upload(&s->d_list, s->plan.list);
+    if (rc == RT_OK) rc = upload(&s->d_lvl, s->plan.lvl);
+    if (rc == RT_OK) rc = upload(&s->d_grp, s->plan.grp);
+    if (rc == RT_OK && !s->d_flag && hipMalloc(&s->d_flag, 16) != hipSuccess) rc = fail(RT_ERR_HIP, "hipMalloc failed");
+    if (rc != RT_OK) {
+        for (void **p : {&s->d_slot_of, &s->d_slot_box, &s->d_list, &s->d_lvl, &s->d_grp}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return rc;
+    }
+    std::vector<float>().swap(s->pbox);   // the boxes and the schedule live on the device from here on
+    for (std::vector<uint32_t> *v : {&s->plan.slot_of, &s->plan.list, &s->plan.lvl, &s->plan.grp}) std::vector<uint32_t>().swap(*v);
+    s->refit_ready = true;
+    return RT_OK;
+}
+
+static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
+    int rc = ensure_refit(s);
+    if (rc != RT_OK) return rc;
+    // the finite check is a pass of its own, read back before anything is written
+    uint32_t bad = 0;
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
+    launch_check_finite(verts_dev, 9u * count, (uint32_t *)s->d_flag, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: a vertex is NaN or infinite");
+    RefitArgs A{};
+    A.nodes = (float4 *)s->d_nodes; A.prims = (float4 *)s->d_prims; A.shade = (float4 *)s->d_shade;
+    A.slot_box = (float4 *)s->d_slot_box;
+    A.slot_of = (const uint32_t *)s->d_slot_of; A.list = (const uint32_t *)s->d_list;
+    A.lvl = (const uint32_t *)s->d_lvl; A.grp = (const uint32_t *)s->d_grp;
+    A.margin = s->view.walk_margin;
+    A.sliver_lim = s->sliver_lim;
+    launch_update_tris(A, first, count, verts_dev, st);
+    launch_refit(A, s->plan.ntreelets, s->plan.has_top, st);
+    HIP_TRY(hipGetLastError());
+    s->bvh_stale = true;
+    float4 root[2];
+    HIP_TRY(hipMemcpyAsync(root, s->d_nodes, sizeof(root), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const float rb[6] = {root[0].x, root[0].y, root[0].z, root[0].w, root[1].x, root[1].y};
+    bool finite = s->boxes_finite;
+    for (float f : rb) finite = finite && std::isfinite(f);
+    s->view.bounds_finite = finite ? 1 : 0;
+    if (finite) s->nested = true;   // every box is now the union of finite boxes below it
+    return RT_OK;
+}
+
+int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null scene");
+    if (count == 0) return RT_OK;
+    if (!verts_dev) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null vertices");
+    if (s->bvh.indices.size() != s->num_prims)
+        return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles: an SBVH scene (leaves share primitives) cannot be refitted");
+    if (s->quads) return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles: scene built with two-level node records (RT_PT_QUADS=1)");
+    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: range outside the primitives");
+    for (uint32_t id = first; id < first + count; ++id)
+        if ((s->pinfo[id] & 0x7f) != RT_TRIANGLE)
+            return fail(RT_ERR_INVALID, "rt_scene_update_triangles: primitive " + std::to_string(id) + " is not a triangle");
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return update_triangles(s, first, count, verts_dev, (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_scene_update_triangles: ") + e.what());
+    }
+}
+
+int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: null scene");
+    if (count == 0) return RT_OK;
+    if (!verts) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: null vertices");
+    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: range outside the primitives");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+    const size_t need = 36 * (size_t)count;
+    if (need > s->scratch_bytes) {
+        if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
+        s->d_scratch = nullptr;
+        s->scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&s->d_scratch, need));
+        s->scratch_bytes = need;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_scratch, verts, need, hipMemcpyHostToDevice, s->stream));
+    return rt_scene_update_triangles(s, first, count, (const float *)s->d_scratch, s->stream);
 }
 
 int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {

@@ -947,6 +947,73 @@ int rt_bvh_build_host(const rt_prim *prims, const float *transforms, uint32_t n,
     return RT_OK;
 }
 
+// The device refit (rt_refit.hip) restated on the host: leaves as Scene::UpdateNodeBounds
+// (template/scene.h:855-865) over their primitives, interior nodes the union of their children,
+// children before parents.  The nodes are written only when the whole tree checked out.
+int rt_bvh_refit_host(const rt_prim *prims, const float *transforms, uint32_t n, void *nodes, uint32_t nodes_used,
+                      const uint32_t *indices) {
+    if (!prims || !nodes || !indices || n == 0 || nodes_used < 2) return fail(RT_ERR_INVALID, "rt_bvh_refit_host: null or empty argument");
+    try {
+        std::vector<Node> N(nodes_used);
+        std::memcpy(N.data(), nodes, sizeof(Node) * nodes_used);
+        std::vector<uint8_t> seen(n, 0);
+        for (uint32_t k = 0; k < n; ++k) {
+            if (indices[k] >= n) return fail(RT_ERR_INVALID, "rt_bvh_refit_host: primitive index out of range");
+            if (seen[indices[k]]) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: a primitive sits in two leaves (an SBVH); plain trees only");
+            seen[indices[k]] = 1;
+        }
+        std::vector<uint32_t> order, st{0u};
+        std::vector<uint8_t> slot(n, 0);
+        while (!st.empty()) {   // pre-order; children in range, every leaf slot met once
+            const uint32_t k = st.back();
+            st.pop_back();
+            if (order.size() >= nodes_used) return fail(RT_ERR_INVALID, "rt_bvh_refit_host: the tree has a cycle");
+            order.push_back(k);
+            const Node &nd = N[k];
+            if (nd.count > 0) {
+                if ((uint64_t)nd.leftFirst + nd.count > n)
+                    return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: a leaf reaches past the n indices (an SBVH); plain trees only");
+                for (uint32_t s = nd.leftFirst; s < nd.leftFirst + nd.count; ++s) {
+                    if (slot[s]) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: leaves overlap; plain trees only");
+                    slot[s] = 1;
+                }
+                continue;
+            }
+            if (nd.leftFirst < 2 || (uint64_t)nd.leftFirst + 1 >= nodes_used)
+                return fail(RT_ERR_INVALID, "rt_bvh_refit_host: child pair out of range");
+            st.push_back(nd.leftFirst + 1);
+            st.push_back(nd.leftFirst);
+        }
+        for (size_t i = order.size(); i-- > 0;) {
+            Node &nd = N[order[i]];
+            f3 mn, mx;
+            if (nd.count > 0) {
+                mn = mk(1e30f, 1e30f, 1e30f);
+                mx = mk(-1e30f, -1e30f, -1e30f);
+                for (uint32_t s = nd.leftFirst; s < nd.leftFirst + nd.count; ++s) {
+                    const uint32_t id = indices[s];
+                    PrimX x;
+                    PrimGeom g;
+                    prim_transform(prims[id], transforms ? transforms + 16 * (size_t)id : nullptr, x);
+                    prim_geometry(prims[id], x, g);
+                    mn = fmin3(mn, g.bmin);
+                    mx = fmax3(mx, g.bmax);
+                }
+            } else {
+                const Node &l = N[nd.leftFirst], &r = N[nd.leftFirst + 1];
+                mn = fmin3(mk(l.mn[0], l.mn[1], l.mn[2]), mk(r.mn[0], r.mn[1], r.mn[2]));
+                mx = fmax3(mk(l.mx[0], l.mx[1], l.mx[2]), mk(r.mx[0], r.mx[1], r.mx[2]));
+            }
+            nd.mn[0] = mn.x; nd.mn[1] = mn.y; nd.mn[2] = mn.z;
+            nd.mx[0] = mx.x; nd.mx[1] = mx.y; nd.mx[2] = mx.z;
+        }
+        std::memcpy(nodes, N.data(), sizeof(Node) * nodes_used);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_bvh_refit_host: ") + e.what());
+    }
+}
+
 int rt_sbvh_build_host(const rt_prim *prims, const float *transforms, uint32_t n, void **nodes, uint32_t **indices,
                        rt_scene_info *info) {
     if (!prims || !nodes || !indices) return fail(RT_ERR_INVALID, "rt_sbvh_build_host: null argument");

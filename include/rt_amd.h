@@ -158,6 +158,14 @@ int rt_recipe_describe(const char *name, const char *mesh_dir, rt_prim *prims, u
  * transforms as in rt_scene_desc (NULL = identity) */
 int rt_bvh_build_host(const rt_prim *prims, const float *transforms, uint32_t n, void *nodes, uint32_t *indices,
                       rt_scene_info *info);
+/* The refit of rt_scene_update_triangles on the host, no device: the boxes of nodes (nodes_used x 32 B,
+ * the topology rt_bvh_build_host or a caller made) rewritten in place for prims[n] -- a leaf's box is
+ * the min / max over its primitives' boxes (Scene::UpdateNodeBounds, template/scene.h:855-865), an
+ * interior node's the union of its children's; leftFirst / count untouched.  With the primitives the
+ * tree was built from it returns rt_bvh_build_host's bytes.  A plain tree only (every primitive in
+ * exactly one leaf): RT_ERR_UNSUPPORTED for an SBVH's index array; the nodes are untouched on error. */
+int rt_bvh_refit_host(const rt_prim *prims, const float *transforms, uint32_t n, void *nodes, uint32_t nodes_used,
+                      const uint32_t *indices);
 /* the opt-in spatial-split BVH (RT_BVH_SBVH) on the host: library-allocated nodes
  * (info->nodes_used x 32 B) and primitive-index array (info->num_refs; primitives may
  * repeat); free both with rt_free */
@@ -191,8 +199,30 @@ int rt_scene_get_info(const rt_scene *s, rt_scene_info *info);
  * environment forces LANE / WAVE at scene creation. */
 enum { RT_WALK_LANE = 0, RT_WALK_WAVE = 1, RT_WALK_AUTO = 2 };
 int rt_scene_set_camera_walk(rt_scene *s, int walk);
-/* host copy of the BVH in use (nodes_used x 32 B, num_refs x u32), in the reference's node order */
+/* host copy of the BVH in use (nodes_used x 32 B, num_refs x u32), in the reference's node order;
+ * after rt_scene_update_triangles the first call downloads the refitted boxes */
 int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
+/* Animated geometry (the reference's "optionally animated" scene: Scene::SetTime, template/scene.h:213-224,
+ * and Tick's animation branch, renderer.cpp:206-237).  Replace the vertices of triangle primitives
+ * [first, first + count) and refit the BVH in place: topology, primitive ids, materials and leaf
+ * membership are unchanged; the triangles' device records become those of a fresh rt_scene_create on
+ * the new vertices, every node box the exact union of what lies below it (min / max of floats: no
+ * rounding), and the wave walk's sticky boxes are recomputed.  verts_dev: DEVICE float[9 * count],
+ * world-space A, B, C per triangle as rt_prim.v.  Blocks: it first waits for all outstanding work on
+ * the scene's device (renderers run frames on their own streams), runs on `stream`, and returns when
+ * the scene is ready for any stream.  The caller renders the next frame with reset = 1, as the
+ * reference does (renderer.cpp:237).  Renderers keep their timed choices, tile orders and deals
+ * (speed only; frames are identical under any of them), and the scene keeps its camera-walk policy.
+ * The first update of a scene builds its refit plan (host, one pass over the tree).
+ *   RT_ERR_INVALID      null pointer, range outside the primitives, a non-triangle primitive in the
+ *                       range, or a NaN / infinite vertex -- the scene is untouched (the vertices are
+ *                       checked in a pass of their own before anything is written);
+ *   RT_ERR_UNSUPPORTED  an SBVH scene (num_refs != num_prims), or one built with RT_PT_QUADS=1.
+ * count == 0 is RT_OK and does nothing.  Moving spheres, quads, cubes or the light, and topology
+ * changes, need a new scene. */
+int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream);
+/* the same with the vertices in host memory (staged on the scene's private stream) */
+int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts);
 
 /* Batched Scene::IntersectBVH (template/scene.h:285-320): rays_dev[n] -> hits_dev[n]. */
 int rt_intersect(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, uint32_t n, void *stream);

@@ -253,6 +253,16 @@ class Scene {   // template/scene.h:37
         rt_check(rt_occluded_host(handle(), in.data(), out.data(), (uint32_t)in.size()));
         return std::vector<bool>(out.begin(), out.end());
     }
+    // Animated meshes (the host's Scene::SetTime, template/scene.h:213-224): new world-space vertices
+    // A, B, C (9 floats each, host memory) for triangle primitives [first, first + count) and an
+    // in-place BVH refit; the next Tick resets the accumulator as the reference's does (renderer.cpp:237)
+    void UpdateTriangles(uint32_t first, const float *verts, uint32_t count) {
+        rt_check(rt_scene_update_triangles_host(handle(), first, count, verts));
+    }
+    // the same with the vertices already in device memory, on a hipStream_t
+    void UpdateTrianglesDevice(uint32_t first, const float *verts_dev, uint32_t count, void *stream = nullptr) {
+        rt_check(rt_scene_update_triangles(handle(), first, count, verts_dev, stream));
+    }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
