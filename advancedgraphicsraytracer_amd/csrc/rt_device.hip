@@ -33,6 +33,7 @@
 #include "rt_dev_types.h"
 #include "rt_internal.h"
 #include "rt_refit.h"
+#include "rt_tune.h"
 
 
 
@@ -156,8 +157,6 @@ struct rt_renderer {
     uint32_t *d_rgb = nullptr;   // staging frame for rt_render_frame_host
     uint64_t primary = 0, frames = 0;
     hipStream_t stream = nullptr;
-    // RT_WALK_AUTO: the first eligible frames time the lane walk and the wave walk on the
-    // caller's stream (one warm-up, one each), the fourth picks the faster for good
     // measured-cost tile order (tile_order_step): per-tile cycles of one frame (two cost
     // maps while the camera walk is being timed), longest tile first afterwards
     uint32_t *d_order = nullptr, *d_cost = nullptr;
@@ -170,20 +169,18 @@ struct rt_renderer {
                                 // order (path-traced frames)
     uint32_t order_split = 0;   // leading tiles of the split order that run as order_parts units each
     uint32_t order_parts = 2;
-    int split_phase = -1;       // -1 decided / not tried; 0 .. 4 kTuneGroup - 1 timing frames in groups
-                                // (plain, split, split, plain), 4 kTuneGroup decide
-    bool use_split = false;     // the split order measured faster
-    hipEvent_t sev[8] = {};     // split timing: events 2i, 2i+1 around timing frame i
-    float split_ms[4] = {};
-    int tune = 0;                   // camera walk: 0 warm-up, 1 .. kWalkTimed timed frames, kTuneDecide, kTuneDone
+    // The timed choices (rt_tune.h) -- camera walk lane / wave, plain / split order, frames in flight --
+    // each with its schedule, the events around its groups, the group times and what they decided
+    TimedGroups walk_tg, split_tg, ps_tg;
+    hipEvent_t tune_ev[4][16] = {};   // [kWalk / kSplit / kOverlap][2g, 2g + 1 around group g], [kGate][start, probe]
+    float walk_ms[4] = {}, split_ms[4] = {}, ps_ms[8] = {};
+    int wave = -1;                  // the wave walk measured faster: 1 / 0, -1 not decided yet
+    bool use_split = false;         // the split order measured faster
+    int ps_use = -1;                // frames in flight (0 = serial), -1 not decided yet
+    uint64_t walk_key = 0;          // the parameter set whose frames the walk timing runs on
     hipEvent_t stall_ev = nullptr;  // after the previous frame while a timed group runs (kTuneRestarts)
     bool stall_armed = false;
-    int walk_restarts = 0, split_restarts = 0, ps_restarts = 0;   // restarts of group *_rg
-    int walk_rg = -1, split_rg = -1, ps_rg = -1;
-    bool wave = false;
-    uint64_t tune_key = 0;          // the parameter set whose frames the walk timing ran on
     int walk_check = RT_WALK_CHECK_OFF;     // rt_renderer_set_walk_check
-    hipEvent_t tev[8] = {};         // walk timing: events 2g, 2g + 1 around group g
     // wavefront path tracer (PathArgs): two path-state slots (state, records, queues), grown on
     // demand, each owned by one of the renderer's two path streams.  Sample batches alternate
     // between them, so one batch's (or the next frame's) level 0 fills the CUs that the other
@@ -210,21 +207,14 @@ struct rt_renderer {
     uint32_t pt_nslots = 0;         // slots in use, decided for path state of up to pt_need bytes
     size_t pt_need = 0;
     bool pt_serial_last = false;    // the last path-traced frame ran the serial path
-    // overlapped primary+shadow frames (launch_render): with RT_PS_PIPELINE auto, eight groups
-    // of kPsGroup eligible frames back to back -- serial, 2 in flight, 4, 6, 6, 4, 2, serial (or
-    // four: serial, 2, 2, serial), so that a clock drift cancels -- are timed on the caller's
-    // stream (events pev[2g], pev[2g + 1] around group g); the next frame keeps the fastest mode
-    // for the parameter set, and the result buffers it does not use are freed
-    int ps_phase = 0;               // 0 .. groups x G - 1 timing frames (G = kPsGroup, 2 kPsGroup for 8
-                                    // groups), then decide; -1 decided
-    int ps_groups = 0;              // timed groups of this decision (4: serial / 2; 8: serial / 2 / 4 / 6)
-    uint32_t ps_use = 0;            // decided: frames in flight (0 = serial)
+    // overlapped primary+shadow frames (overlap_step): with RT_PS_PIPELINE auto, groups of
+    // eligible frames back to back at each candidate depth are timed on the caller's stream
+    // (ps_tg); the next frame keeps the fastest mode for the parameter set, and the result
+    // buffers it does not use are freed
     uint64_t ps_last = 0;           // r->frames at the last timing frame (any other frame restarts)
     uint32_t ps_prev = 0;           // frames in flight of the previous eligible frame (0 serial)
-    hipEvent_t pev[16] = {};
     hipEvent_t ps_join = nullptr;   // caller's stream -> overlap stream, on a switch to overlapped
     hipEvent_t cost_ev = nullptr;   // path-traced frames: the cost map was cleared (caller's stream)
-    float ps_ms[8] = {};
     // the overlapped frames' per-sample results, frame n in buffer n % buffers (kernel on
     // renderer stream n % depth): frame n + buffers waits for the finishing pass of frame n only,
     // so a kernel never waits for the finish of a frame still running beside it
@@ -239,7 +229,6 @@ struct rt_renderer {
     uint64_t gate_key = 0;
     int gate_state = 0;             // 0 start, 1 running, 2 probe recorded, 3 open
     uint32_t gate_frames = 0;
-    hipEvent_t gate_ev[2] = {};
     // per-sample values of sample-split frames (FrameArgs::samples)
     void *d_samples = nullptr;
     size_t samples_bytes = 0;
@@ -268,32 +257,7 @@ namespace {
 inline float ubits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 inline float ibits(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
 
-// The timed choices between two variants (camera walk, split order) time four groups of
-// kTuneGroup frames in the order A, B, B, A (a clock drift over the groups cancels) and keep
-// the faster -- single frames were too noisy to decide on (ranks with equal work came out 35 %
-// apart in round-3 shard timings)
-constexpr int kTuneGroup = 4;
-// A timed choice between the default (groups 0 and 3) and an alternative (groups 1 and 2),
-// groups run A, B, B, A: the alternative must win by kTuneMargin.  The palindrome cancels a
-// linear clock drift, not a first group that still runs slow: TEAPOT-F 1080p timed its plain
-// order at 0.4986 / 0.4195 ms per group against 0.4531 / 0.4551 for the half-tile split, whose
-// sum looked 1 % faster -- and its frames then ran at 0.114 instead of 0.104 ms (bench config 2
-// after a config-4 run on the same box, round 3).  The choices that pay win by 8-40 %.
-constexpr float kTuneMargin = 0.03f;
-inline bool tuned_alternative(const float ms[4]) {
-    return ms[1] + ms[2] < (ms[0] + ms[3]) * (1.0f - kTuneMargin);
-}
-constexpr int kWalkTimed = 4 * kTuneGroup;
-constexpr int kTuneDecide = 1 + kWalkTimed, kTuneDone = kTuneDecide + 1;
-// A timed group assumes frames submitted back to back.  When the caller synchronises inside a
-// group (bench.py's clock ramp every 20 frames, multi_overhead.py every 50), the GPU idles between
-// two of its frames and the group times the host, not the frames: TEAPOT-F 1080p with 8 hardware
-// queues timed its first serial group at 2.48 ms against 1.58 for the last, picked 2 frames in
-// flight and ran at 0.0995 ms against 0.097 serial (round 5, profiles/r05/hwq/).  So while a group
-// runs, an event after each frame is queried when the next frame is submitted: if the previous
-// frame had already completed, the GPU ran dry in between and the group restarts (at most
-// kTuneRestarts times per group, so a caller that syncs every frame still gets a decision).
-constexpr int kTuneRestarts = 4;
+enum { kWalk, kSplit, kOverlap, kGate };   // rt_renderer::tune_ev rows
 
 // LDS stack entries per lane: a traversal pushes at most one entry per tree level, so the tree
 // depth is enough.  Rounding it up to 8 cost occupancy where the stacks bound the workgroups
@@ -945,6 +909,19 @@ int set_tile_map(rt_renderer *r, const uint32_t *tiles, uint32_t n, uint32_t nti
 // follows frame n + 1's levels on the caller's stream; slots + 1 buffers let a frame start
 // behind the finish of the frame `slots` back.
 
+// The first n timing events of a row of rt_renderer::tune_ev, created as first needed.
+int ensure_events(hipEvent_t *ev, int n) {
+    if (!ev[0])
+        for (int k = 0; k < n; ++k) HIP_TRY(hipEventCreate(&ev[k]));
+    return RT_OK;
+}
+// The measured time of each timed group, once the last group's end event has completed.
+int group_times(const hipEvent_t *ev, int groups, float *ms) {
+    HIP_TRY(hipEventSynchronize(ev[2 * groups - 1]));
+    for (int g = 0; g < groups; ++g) HIP_TRY(hipEventElapsedTime(&ms[g], ev[2 * g], ev[2 * g + 1]));
+    return RT_OK;
+}
+
 // The renderer's overlap streams 0 .. n-1 and their ordering events, created as first needed.
 // Only as many as a mode uses: each stream becomes a hardware queue of its own (up to
 // GPU_MAX_HW_QUEUES), and with 8 queues, creating all 8 streams for a timing that used 2 left
@@ -977,7 +954,7 @@ int ensure_res(rt_renderer *r, int par, uint64_t bytes) {
     return RT_OK;
 }
 
-// Overlapped primary+shadow frames' result buffer b, grown to `bytes` (launch_render).
+// Overlapped primary+shadow frames' result buffer b, grown to `bytes` (overlap_step).
 int ensure_ps_res(rt_renderer *r, uint32_t b, uint64_t bytes) {
     if (!r->ps_fin[b]) HIP_TRY(hipEventCreateWithFlags(&r->ps_fin[b], hipEventDisableTiming | hipEventReleaseToDevice));
     if (bytes <= r->ps_res_bytes[b]) return RT_OK;
@@ -1000,7 +977,7 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
     // camera rays of level 0 take the wave-coherent walk when the scene forces it, or when
     // the renderer's primary+shadow frames timed it faster (RT_WALK_AUTO)
     view.wave_primary = !s->has_cubes && s->nested && s->walk_fits &&
-                        (s->walk == RT_WALK_WAVE || (s->walk == RT_WALK_AUTO && r->tune == kTuneDone && r->wave));
+                        (s->walk == RT_WALK_WAVE || (s->walk == RT_WALK_AUTO && r->wave > 0));
     view.walk_stats = r->d_counters;
     view.walk_check = r->walk_check;
     view.quad_lanes = s->quad_lanes ? 1 : 0;
@@ -1251,38 +1228,55 @@ void frame_build(const rt_renderer *r, const SceneView &view, const FrameArgs &F
     L.waves = 8;
 }
 
-int tile_order_step(rt_renderer *r, FrameArgs &F, uint64_t key, int walk_phase, bool split_ok, bool gate_open,
-                    bool stalled, int &split_ev0, int &split_ev1) {
-    split_ev0 = split_ev1 = -1;
-    const uint32_t n = F.ntiles_local;
-    if (key != r->order_key || n != r->order_n) {
-        r->order_key = key;
-        r->order_state = 0;
-        r->host_cost.clear();
-        r->tail_bound = false;
-        r->ps_phase = 0;   // the overlap decision belongs to the parameter set too
-        r->ps_restarts = 0;
-        r->ps_rg = -1;
-        if (n != r->order_n) {
-            HIP_TRY(hipDeviceSynchronize());                             // frames may still read them
-            if (r->d_order) HIP_TRY(hipFree(r->d_order));
-            if (r->d_cost) HIP_TRY(hipFree(r->d_cost));
-            r->d_order = r->d_cost = nullptr;
-            r->order_n = 0;
-            // plain order (n) | split order: n + (parts - 1) x the split tiles -- up to 9 n with 8 parts
-            // and every tile split (RT_SPLIT_PARTS / RT_SPLIT_HEAVY; 3 n overflowed a balanced rank's
-            // short tile list with 4 parts and 500 split tiles, round 5)
-            HIP_TRY(hipMalloc(&r->d_order, 9u * n * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc(&r->d_cost, 2u * n * sizeof(uint32_t)));   // one cost map per camera walk
-            r->order_n = n;
-        }
+// The tile costs and the order of parameter set `key` with n local tiles: a new set drops what the
+// last one recorded, a new tile count reallocates d_order / d_cost.
+int ensure_order(rt_renderer *r, uint64_t key, uint32_t n) {
+    if (key == r->order_key && n == r->order_n) return RT_OK;
+    r->order_key = key;
+    r->order_state = 0;
+    r->host_cost.clear();
+    if (n != r->order_n) {
+        HIP_TRY(hipDeviceSynchronize());                             // frames may still read them
+        if (r->d_order) HIP_TRY(hipFree(r->d_order));
+        if (r->d_cost) HIP_TRY(hipFree(r->d_cost));
+        r->d_order = r->d_cost = nullptr;
+        r->order_n = 0;
+        // plain order (n) | split order: n + (parts - 1) x the split tiles -- up to 9 n with 8 parts
+        // and every tile split (RT_SPLIT_PARTS / RT_SPLIT_HEAVY; 3 n overflowed a balanced rank's
+        // short tile list with 4 parts and 500 split tiles, round 5)
+        HIP_TRY(hipMalloc(&r->d_order, 9u * n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&r->d_cost, 2u * n * sizeof(uint32_t)));   // one cost map per camera walk
+        r->order_n = n;
     }
+    return RT_OK;
+}
+
+// What the steps of one primary+shadow / Whitted frame (launch_render) hand to each other.
+struct FramePlan {
+    uint64_t key = 0;                           // the frame's parameter set (param_key)
+    bool gate_open = false, stalled = false;    // tune_gate; the GPU ran dry since the previous frame
+    TimedFrame walk, split, ps;                 // tune_ev[kWalk / kSplit / kOverlap] around this launch
+    int cost_map = -1;                          // this frame records the tile costs under walk 0 / 1
+    bool walk_pending = false;                  // the walk was not decided before this frame
+    uint32_t depth = 0, buf = 0, lane = 0;      // frames in flight (0 serial, else 2..6); result buffer, renderer stream
+};
+
+int tile_order_step(rt_renderer *r, FrameArgs &F, bool split_ok, FramePlan &P) {
+    const uint32_t n = F.ntiles_local;
+    // the walk: costs recorded on this frame (0 / 1), decided on it (2), still to be timed (3)
+    const int walk_phase = P.cost_map >= 0 ? P.cost_map : P.walk.decide ? 2 : P.walk_pending ? 3 : -1;
+    if (P.key != r->order_key || n != r->order_n) {
+        r->tail_bound = false;
+        r->ps_tg.stop();   // the overlap decision belongs to the parameter set too
+        r->ps_use = -1;
+    }
+    if (int rc = ensure_order(r, P.key, n); rc != RT_OK) return rc;
     int use = -1;                                                      // cost map to sort this frame
     if (walk_phase == 3) {
         // walk timing not started yet: record nothing
     } else if (r->order_state == 0) {
         if (walk_phase == 0 || walk_phase == 1) F.tile_cost = r->d_cost + (size_t)walk_phase * n;
-        else if (walk_phase == 2) use = r->wave ? 1 : 0;              // recorded on the timed frames
+        else if (walk_phase == 2) use = r->wave;                      // recorded on the timed frames
         else { F.tile_cost = r->d_cost; r->order_state = 1; }
     } else if (r->order_state == 1) {
         use = 0;
@@ -1335,42 +1329,25 @@ int tile_order_step(rt_renderer *r, FrameArgs &F, uint64_t key, int walk_phase, 
         r->order_parts = parts;
         r->order_state = 2;
         r->use_split = k > 0 && r->scene->heavy_split > 0;            // a forced count: no timing
-        r->split_phase = (k > 0 && r->scene->heavy_split < 0) ? 0 : -1;
-        r->split_restarts = 0;
-        r->split_rg = -1;
-        if (r->split_phase == 0 && !r->sev[0])
-            for (auto &e : r->sev) HIP_TRY(hipEventCreate(&e));
+        r->split_tg.stop();
+        if (k > 0 && r->scene->heavy_split < 0) {                      // groups plain, split, split, plain
+            start_two_way(r->split_tg, false);
+            if (int rc = ensure_events(r->tune_ev[kSplit], 8); rc != RT_OK) return rc;
+        }
     }
     if (r->order_state == 2) {
-        bool split = r->use_split;
-        if (r->split_phase == 4 * kTuneGroup) {                        // decide after the timed groups
-            HIP_TRY(hipEventSynchronize(r->sev[7]));
-            for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&r->split_ms[i], r->sev[2 * i], r->sev[2 * i + 1]));
-            r->use_split = split = tuned_alternative(r->split_ms);
-            r->split_phase = -1;
-        } else if (r->split_phase >= 0 && gate_open) {
-            if (r->split_phase / kTuneGroup != r->split_rg) {
-                r->split_rg = r->split_phase / kTuneGroup;
-                r->split_restarts = 0;
-            }
-            if (stalled && r->split_phase % kTuneGroup != 0 && r->split_restarts < kTuneRestarts) {
-                r->split_phase -= r->split_phase % kTuneGroup;                 // redo the group
-                ++r->split_restarts;
-            }
-            const int g = r->split_phase / kTuneGroup, i = r->split_phase % kTuneGroup;   // plain, split, split, plain
-            split = g == 1 || g == 2;
-            split_ev0 = i == 0 ? 2 * g : -1;
-            split_ev1 = i == kTuneGroup - 1 ? 2 * g + 1 : -1;
-            ++r->split_phase;
+        P.split = r->split_tg.next(P.gate_open, P.stalled);
+        if (P.split.decide) {
+            if (int rc = group_times(r->tune_ev[kSplit], 4, r->split_ms); rc != RT_OK) return rc;
+            r->use_split = tuned_alternative(r->split_ms);
         }
+        const bool split = P.split.group >= 0 ? alternative_group(P.split) : r->use_split;
         F.order = split ? r->d_order + n : r->d_order;
         F.nunits = F.ntiles_local * F.nchunks + (split ? r->order_split * (r->order_parts - 1u) : 0u);   // split only with nchunks 1
         F.part_shift = r->order_parts == 8 ? 3u : r->order_parts == 4 ? 4u : 5u;
     }
     return RT_OK;
 }
-
-constexpr int kPsGroup = 16;  // frames per timed group of the overlap decision (8 in round 3)
 
 // the parameter set a frame belongs to (the tuned choices and the tile order are per set)
 uint64_t param_key(const rt_renderer *r, const FrameArgs &F, const rt_camera *cam, const rt_frame_params *p) {
@@ -1392,20 +1369,19 @@ int tune_gate(rt_renderer *r, uint64_t key, hipStream_t st, bool &open) {
     if (delay <= 0.0f) r->gate_state = 3;
     if (r->gate_state == 3) { open = true; return RT_OK; }
     open = false;
-    if (!r->gate_ev[0])
-        for (auto &e : r->gate_ev) HIP_TRY(hipEventCreate(&e));
+    if (int rc = ensure_events(r->tune_ev[kGate], 2); rc != RT_OK) return rc;
     if (r->gate_state == 0) {
-        HIP_TRY(hipEventRecord(r->gate_ev[0], st));
+        HIP_TRY(hipEventRecord(r->tune_ev[kGate][0], st));
         r->gate_state = 1;
         r->gate_frames = 0;
     } else if (r->gate_state == 1) {
         if (++r->gate_frames % 8 == 0) {
-            HIP_TRY(hipEventRecord(r->gate_ev[1], st));
+            HIP_TRY(hipEventRecord(r->tune_ev[kGate][1], st));
             r->gate_state = 2;
         }
-    } else if (hipEventQuery(r->gate_ev[1]) == hipSuccess) {   // state 2: the probe has run
+    } else if (hipEventQuery(r->tune_ev[kGate][1]) == hipSuccess) {   // state 2: the probe has run
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, r->gate_ev[0], r->gate_ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, r->tune_ev[kGate][0], r->tune_ev[kGate][1]));
         r->gate_state = ms >= delay ? 3 : 1;
         open = r->gate_state == 3;
     }
@@ -1491,6 +1467,223 @@ int work_frame(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
     return RT_OK;
 }
 
+// Sample split: a frame (or a shard of one) with few tiles and several samples per pixel is cut
+// into (tile, sample chunk) units, so the dispatcher still balances about s->split_units waves of
+// uneven cost (a 1/8 shard at spp 8 would otherwise be one round of whole-tile waves, as long as
+// its slowest tile); the units' samples go to d_samples.
+// (first measured on TEAPOT-F shards, tools/shard_time.py: split below ~5 rounds of
+// waves, until ~10 rounds, chunks of equal sample counts.  Round 3: whole 1080p frames at
+// spp > 1 gain from it too -- CFG5-sub scene spp 16 2.41 -> 1.44 ms, mig29 x16 spp 4 1.49
+// -> 0.76 ms, TEAPOT-F spp 4 0.390 -> 0.386 ms, frames identical (profiles/r03/split_ab/) --
+// so the threshold is 40,000 tiles instead of 20,000; 80,000 measured the same or slower)
+int sample_split(rt_renderer *r, uint32_t spp, bool eligible, FrameArgs &F) {
+    const rt_scene *s = r->scene;
+    F.nchunks = 1;
+    if (eligible && spp > 1 && F.ntiles_local < s->split_units)
+        while (F.ntiles_local * F.nchunks < 2u * s->split_units && F.nchunks < spp) {
+            uint32_t d = F.nchunks + 1;                  // next divisor of spp: equal chunks
+            while (spp % d) ++d;
+            F.nchunks = d;
+        }
+    F.nunits = F.ntiles_local * F.nchunks;
+    if (F.nchunks > 1) {
+        const size_t need = sizeof(float4) * (size_t)spp * F.ntiles_local * 64u;
+        if (need > r->samples_bytes) {
+            if (r->d_samples) HIP_TRY(hipFree(r->d_samples));
+            r->d_samples = nullptr;
+            r->samples_bytes = 0;
+            HIP_TRY(hipMalloc(&r->d_samples, need));
+            r->samples_bytes = need;
+        }
+        F.samples = static_cast<float4 *>(r->d_samples);
+    }
+    return RT_OK;
+}
+
+// A path-traced (depth >= 2) frame through the wavefront tracer, with the per-tile cost map of a
+// path-traced parameter set (rt_renderer_tile_costs, the multi-GPU deal's input): each tile's
+// level-0 wave cycles -- its camera rays, their shading and NEE, summed over the samples -- recorded
+// on the set's first frame, read on its second (one device synchronisation per set); the bounce levels
+// follow the camera level's hits, so a sky tile is cheap at every level.  No tile order is built from it.
+int wavefront_frame(rt_renderer *r, const FrameArgs &F, const rt_camera *cam, const rt_frame_params *p, hipStream_t st) {
+    rt_scene *s = r->scene;
+    uint32_t *rec_cost = nullptr;
+    if (s->tile_order) {
+        const uint32_t n = F.ntiles_local;
+        if (int rc = ensure_order(r, param_key(r, F, cam, p), n); rc != RT_OK) return rc;
+        if (r->order_state == 0) {
+            if (!r->cost_ev) HIP_TRY(hipEventCreateWithFlags(&r->cost_ev, hipEventDisableTiming | hipEventReleaseToDevice));
+            HIP_TRY(hipMemsetAsync(r->d_cost, 0, n * sizeof(uint32_t), st));
+            HIP_TRY(hipEventRecord(r->cost_ev, st));
+            rec_cost = r->d_cost;
+            r->order_state = 1;
+        } else if (r->order_state == 1) {
+            HIP_TRY(hipDeviceSynchronize());                                 // the recording frame is done
+            r->host_cost.resize(n);
+            HIP_TRY(hipMemcpy(r->host_cost.data(), r->d_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            r->order_state = 3;                                              // costs held, no order
+        }
+    }
+    return launch_pt_frame(r, F, s->view, !s->view.sky_const, st, rec_cost);
+}
+
+// Camera-ray walk of this frame (only the global-node primary+shadow kernel, `walk_kernel`, has both).
+// RT_WALK_AUTO times lane against wave (walk_tg: groups lane, wave, wave, lane) and keeps the faster.
+int walk_step(rt_renderer *r, bool walk_kernel, SceneView &view, FramePlan &P) {
+    const rt_scene *s = r->scene;
+    const bool timed = walk_kernel && s->walk == RT_WALK_AUTO;
+    // the walk's timed groups must all run on one parameter set's frames: a set change in the
+    // middle (a multi-GPU deal switch, a camera move) restarts them from the warm-up
+    if (timed && r->walk_tg.running() && P.key != r->walk_key) r->walk_tg.reset();
+    if (!r->walk_tg.running()) r->walk_key = P.key;
+    P.walk_pending = timed && r->wave < 0;
+    if (walk_kernel && s->walk == RT_WALK_WAVE) view.wave_primary = 1;
+    if (P.walk_pending) {
+        if (int rc = ensure_events(r->tune_ev[kWalk], 8); rc != RT_OK) return rc;
+        P.walk = r->walk_tg.next(P.gate_open, P.stalled);
+        if (P.walk.decide) {
+            if (int rc = group_times(r->tune_ev[kWalk], 4, r->walk_ms); rc != RT_OK) return rc;
+            r->wave = tuned_alternative(r->walk_ms) ? 1 : 0;
+        } else if (P.walk.group >= 0) {
+            view.wave_primary = alternative_group(P.walk) ? 1 : 0;
+            P.cost_map = walk_cost_map(P.walk);   // each walk's tile costs, on its first frame
+        }
+    }
+    if (timed && r->wave >= 0) view.wave_primary = r->wave;
+    return RT_OK;
+}
+
+// Overlapped primary+shadow frames: each pixel's accumulator update has to follow the previous
+// frame's, but its traversal does not.  Once the frame is in its steady state (no timing events, no
+// cost recording: `ps_ok`) the frame kernel runs on one of the renderer's overlap streams (by frame
+// count) and stores its samples in a frame-level result buffer; a finishing pass on the caller's
+// stream then does the running average + RGB8 (k_pt_finish, the same float operations as the
+// kernel's own epilogue). Frame f+1's waves so fill the CUs that frame f's tail leaves idle.  The
+// kernel touches only renderer-private memory; a stream waits only for the finishing pass that last
+// read its result buffer.
+// Three result buffers (RT_PS_BUFFERS): with two, frame f + 2's kernel waited for frame f's
+// finishing pass while frame f + 1's kernel shared the CUs, which put the finishing pass and two
+// cross-stream waits on the critical path (TEAPOT-F 1080p 0.119 ms per frame vs 0.1055 with three;
+// four measure the same as three; profiles/r02/ps_window*.log).
+// It pays where a frame is latency- or tail-bound (mig29 x16 1080p 0.41 -> 0.33 ms, 720p 0.385 ->
+// 0.255 ms) and costs where it is issue-bound (TEAPOT-F 1080p 0.1024 -> 0.1055 ms: the finishing
+// pass's extra 66 MB of sample traffic is not hidden there), and only when the caller submits
+// frames back to back.  A small frame -- a multi-GPU rank's 1/N shard, about one round of resident
+// waves -- is one latency chain long, and more frames in flight keep filling its idle issue slots:
+// up to 6 renderer streams (round 3).  So by default each renderer times serial, 2, 4 and 6 frames
+// in flight on its own frames and keeps the fastest (RT_PS_PIPELINE: -1 auto, 0 off, 1 on with
+// RT_PS_DEPTH frames in flight).
+// The timing's events go on the caller's stream after a frame: a group is timed from one frame's
+// completion to another's, in steady state.  (Events before the first frame timed a deeper group
+// short: its first kernels start on their streams while the caller's stream still finishes earlier
+// frames; TEAPOT-F shards then picked 4-6 in flight, 0.125-0.144 ms against 0.092 with 2.  Round 4.)
+int overlap_step(rt_renderer *r, FrameArgs &F, FrameLaunch &L, bool ps_ok, uint64_t ps_bytes, hipStream_t st, FramePlan &o) {
+    const rt_scene *s = r->scene;
+    o.depth = (ps_ok && s->ps_pipeline == 1) ? s->ps_depth : 0u;
+    if (ps_ok && s->ps_pipeline < 0 && o.gate_open) {   // (gate closed: timing not started, serial)
+        // a frame of another kind ran between two timing frames: time it all again
+        if (r->ps_tg.running() && r->frames != r->ps_last + 1) r->ps_tg.stop();
+        if (!r->ps_tg.active() && r->ps_use < 0) {
+            // More than 2 frames in flight are candidates only for frames of a few rounds of resident
+            // waves (a multi-GPU rank's small shard, 720p) or whose costliest tile outlasts twice the
+            // frame's throughput time (tail_bound, from the tile-order cost map: mig29 x16 1080p and its
+            // 1/2 shard, 16,200 tiles, 0.222 -> 0.167 ms with 4 in flight; round 4, depth_exp_*.jsonl);
+            // a throughput-bound frame (TEAPOT-F 1080p, 8 rounds) lost with 4 (0.1035 -> 0.114 ms) and
+            // the timing only risked picking them.
+            const bool deep_ok = F.nunits <= 3u * 4u * 5u * s->num_cus || r->tail_bound;
+            // streams, events and every result buffer before the timing
+            const uint32_t maxd = deep_ok ? 6u : 2u, nb = s->ps_buffers ? s->ps_buffers : maxd + 1u;
+            int rc = ensure_events(r->tune_ev[kOverlap], 16);
+            if (rc == RT_OK) rc = ensure_pipe_streams(r, (int)maxd);
+            for (uint32_t k = 0; k < nb && rc == RT_OK; ++k) rc = ensure_ps_res(r, k, ps_bytes);
+            if (rc != RT_OK) return rc;
+            start_overlap(r->ps_tg, deep_ok);
+        }
+        o.ps = r->ps_tg.next(true, o.stalled);
+        if (o.ps.decide) {
+            if (int rc = group_times(r->tune_ev[kOverlap], r->ps_tg.groups, r->ps_ms); rc != RT_OK) return rc;
+            r->ps_use = (int)tuned_depth(r->ps_ms, r->ps_tg.groups);
+            // every timed frame's finishing pass preceded the last event: no buffer is in use, and
+            // the ones the chosen depth never touches are released (a 1080p spp-1 buffer is 33 MB)
+            const uint32_t keep = r->ps_use == 0 ? 0u : (s->ps_buffers ? s->ps_buffers : r->ps_use + 1u);
+            for (uint32_t b = keep; b <= (uint32_t)kPsMaxDepth; ++b) {
+                if (r->ps_res[b]) HIP_TRY(hipFree(r->ps_res[b]));
+                r->ps_res[b] = nullptr;
+                r->ps_res_bytes[b] = 0;
+                r->ps_fin_set[b] = false;
+            }
+        }
+        o.depth = o.ps.group >= 0 ? overlap_depths(r->ps_tg.groups)[o.ps.group] : (uint32_t)r->ps_use;
+        if (o.ps.group >= 0) r->ps_last = r->frames;
+    }
+    if (o.depth > 0) {
+        if (int rc = ensure_pipe_streams(r, (int)o.depth); rc != RT_OK) return rc;
+        // frame n's kernel on renderer stream n % depth, its samples in buffer n % buffers: with
+        // depth + 1 buffers frame n + depth + 1 waits for frame n's finishing pass only, which
+        // follows frame n's kernel alone -- never a kernel still running beside it
+        const uint32_t buffers = s->ps_buffers ? s->ps_buffers : o.depth + 1u;
+        o.buf = r->ps_count % buffers;
+        o.lane = r->ps_count % o.depth;
+        ++r->ps_count;
+        if (int rc = ensure_ps_res(r, o.buf, ps_bytes); rc != RT_OK) return rc;
+        L.stream = r->pt_stream[o.lane];
+        if (r->ps_fin_set[o.buf]) HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_fin[o.buf], 0));
+        const bool timed_from = o.ps.group >= 0 && o.ps.index == r->ps_tg.skip;   // records the group's start event
+        if (!r->ps_prev || timed_from) {
+            // switching from serial frames: start behind the caller's stream; the frame a group is
+            // timed from: every renderer stream starts behind everything before it, so that no
+            // later frame of the group runs beside the previous group's (whose depth differs)
+            if (!r->ps_join) HIP_TRY(hipEventCreateWithFlags(&r->ps_join, hipEventDisableTiming | hipEventReleaseToDevice));
+            HIP_TRY(hipEventRecord(r->ps_join, st));
+            if (timed_from)
+                for (int k = 0; k < r->nstreams; ++k) HIP_TRY(hipStreamWaitEvent(r->pt_stream[k], r->ps_join, 0));
+            else
+                HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_join, 0));
+        }
+        F.samples = r->ps_res[o.buf];
+    }
+    if (ps_ok) r->ps_prev = o.depth;
+    return RT_OK;
+}
+
+// The frame on its streams: the timed choices' events around the kernel, the finishing pass of a
+// frame that stored its samples, and the completion mark of the next submission's stall check.
+int submit_frame(rt_renderer *r, const SceneView &view, const FrameArgs &F, const FrameLaunch &L, const FramePlan &o,
+                 hipStream_t st) {
+    const rt_scene *s = r->scene;
+    if (o.walk.ev_before >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kWalk][o.walk.ev_before], st));
+    if (o.split.ev_before >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kSplit][o.split.ev_before], st));
+    if (s->ext) kext::launch_frame(view, F, L);
+    else kcore::launch_frame(view, F, L);
+    HIP_TRY(hipGetLastError());
+    if (o.walk.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kWalk][o.walk.ev_after], st));
+    if (o.split.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kSplit][o.split.ev_after], st));
+    if (o.depth > 0) {
+        HIP_TRY(hipEventRecord(r->pt_lv[o.lane], L.stream));
+        HIP_TRY(hipStreamWaitEvent(st, r->pt_lv[o.lane], 0));
+    }
+    if (F.samples) {   // the pixels' samples in sample order, running average, RGB8
+        PathArgs P{};
+        P.batch_spp = F.spp;
+        P.result = F.samples;
+        if (s->ext) kext::launch_pt_finish(F, P, true, st);
+        else kcore::launch_pt_finish(F, P, true, st);
+        HIP_TRY(hipGetLastError());
+        if (o.depth > 0) {
+            HIP_TRY(hipEventRecord(r->ps_fin[o.buf], st));
+            r->ps_fin_set[o.buf] = true;
+        }
+    }
+    if (o.ps.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kOverlap][o.ps.ev_after], st));
+    // a timed group is running: mark this frame's completion for the next submission's stall check
+    if (r->walk_tg.running() || r->split_tg.active() || r->ps_tg.active()) {
+        if (!r->stall_ev) HIP_TRY(hipEventCreateWithFlags(&r->stall_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(r->stall_ev, st));
+        r->stall_armed = true;
+    }
+    return RT_OK;
+}
+
 int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t shard, uint32_t nshards,
                   uint32_t *out, int packed, void *stream, const uint32_t *tiles = nullptr, uint32_t ntiles_map = 0,
                   const uint32_t *fwd_src = nullptr, uint32_t *fwd_dst = nullptr) {
@@ -1499,7 +1692,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     rt_scene *s = r->scene;
     FrameArgs F;
     if (int rc = frame_args(r, cam, p, shard, nshards, tiles, ntiles_map, F); rc != RT_OK) return rc;
-    const uint32_t tiles_x = F.tiles_x, tiles_y = (r->H + 7) / 8, ntiles = tiles_x * tiles_y;
+    const uint32_t tiles_x = F.tiles_x, ntiles = tiles_x * ((r->H + 7) / 8);
     if (tiles) {   // (copied only when the map changed: frames of one deal keep the same list)
         if (r->held_kind != 3 || r->held_gen != r->map_gen) {
             r->held_list = r->map_host;
@@ -1517,340 +1710,44 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     F.fwd_dst = fwd_dst;
     if (F.ntiles_local == 0) return RT_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t depth = p->depth;
-    if (depth > 32) return fail(RT_ERR_UNSUPPORTED, "Trace depth above 32");   // = kWHITTED_MAX
-    const int md = max_depth_class(depth);
+    if (p->depth > 32) return fail(RT_ERR_UNSUPPORTED, "Trace depth above 32");   // = kWHITTED_MAX
+    const int md = max_depth_class(p->depth);
     const bool tex = !s->view.sky_const;
     const int mode = (int)p->mode;
-    // sample split: a frame (or a shard of one) with few tiles and several samples per
-    // pixel is cut into (tile, sample chunk) units, so the dispatcher still balances about
-    // s->split_units waves of uneven cost (a 1/8 shard at spp 8 would otherwise be one
-    // round of whole-tile waves, as long as its slowest tile)
-    F.nchunks = 1;
-    const bool wavefront = mode == RT_MODE_PATH && depth >= 2 && s->pt_wavefront;
-    // (first measured on TEAPOT-F shards, tools/shard_time.py: split below ~5 rounds of
-    // waves, until ~10 rounds, chunks of equal sample counts.  Round 3: whole 1080p frames at
-    // spp > 1 gain from it too -- CFG5-sub scene spp 16 2.41 -> 1.44 ms, mig29 x16 spp 4 1.49
-    // -> 0.76 ms, TEAPOT-F spp 4 0.390 -> 0.386 ms, frames identical (profiles/r03/split_ab/) --
-    // so the threshold is 40,000 tiles instead of 20,000; 80,000 measured the same or slower)
-    if (p->spp > 1 && mode != RT_MODE_PACKET && !wavefront && F.ntiles_local < s->split_units)
-        while (F.ntiles_local * F.nchunks < 2u * s->split_units && F.nchunks < p->spp) {
-            uint32_t d = F.nchunks + 1;                  // next divisor of spp: equal chunks
-            while (p->spp % d) ++d;
-            F.nchunks = d;
-        }
-    F.nunits = F.ntiles_local * F.nchunks;
-    if (F.nchunks > 1) {
-        const size_t need = sizeof(float4) * (size_t)p->spp * F.ntiles_local * 64u;
-        if (need > r->samples_bytes) {
-            if (r->d_samples) HIP_TRY(hipFree(r->d_samples));
-            r->d_samples = nullptr;
-            r->samples_bytes = 0;
-            HIP_TRY(hipMalloc(&r->d_samples, need));
-            r->samples_bytes = need;
-        }
-        F.samples = static_cast<float4 *>(r->d_samples);
-    }
-    const dim3 grid((F.nunits + 3) / 4), block(256);
-    const size_t lds = stack_bytes(s);
+    const bool wavefront = mode == RT_MODE_PATH && p->depth >= 2 && s->pt_wavefront;
+    if (int rc = sample_split(r, p->spp, mode != RT_MODE_PACKET && !wavefront, F); rc != RT_OK) return rc;
     if (wavefront) {
-        // per-tile cost map of a path-traced parameter set (rt_renderer_tile_costs, the multi-GPU
-        // deal's input): each tile's level-0 wave cycles -- its camera rays, their shading and
-        // NEE, summed over the samples -- recorded on the set's first frame, read on its second
-        // (one device synchronisation per set); the bounce levels follow the camera level's
-        // hits, so a sky tile is cheap at every level.  No tile order is built from it.
-        uint32_t *rec_cost = nullptr;
-        if (s->tile_order) {
-            const uint64_t pkey = param_key(r, F, cam, p);
-            const uint32_t n = F.ntiles_local;
-            if (pkey != r->order_key || n != r->order_n) {
-                r->order_key = pkey;
-                r->order_state = 0;
-                r->host_cost.clear();
-                if (n != r->order_n) {
-                    HIP_TRY(hipDeviceSynchronize());                             // frames may still read them
-                    if (r->d_order) HIP_TRY(hipFree(r->d_order));
-                    if (r->d_cost) HIP_TRY(hipFree(r->d_cost));
-                    r->d_order = r->d_cost = nullptr;
-                    r->order_n = 0;
-                    HIP_TRY(hipMalloc(&r->d_order, 9u * n * sizeof(uint32_t)));
-                    HIP_TRY(hipMalloc(&r->d_cost, 2u * n * sizeof(uint32_t)));
-                    r->order_n = n;
-                }
-            }
-            if (r->order_state == 0) {
-                if (!r->cost_ev) HIP_TRY(hipEventCreateWithFlags(&r->cost_ev, hipEventDisableTiming | hipEventReleaseToDevice));
-                HIP_TRY(hipMemsetAsync(r->d_cost, 0, n * sizeof(uint32_t), st));
-                HIP_TRY(hipEventRecord(r->cost_ev, st));
-                rec_cost = r->d_cost;
-                r->order_state = 1;
-            } else if (r->order_state == 1) {
-                HIP_TRY(hipDeviceSynchronize());                                 // the recording frame is done
-                r->host_cost.resize(n);
-                HIP_TRY(hipMemcpy(r->host_cost.data(), r->d_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                r->order_state = 3;                                              // costs held, no order
-            }
-        }
-        int rc = launch_pt_frame(r, F, s->view, tex, st, rec_cost);
-        if (rc != RT_OK) return rc;
+        if (int rc = wavefront_frame(r, F, cam, p, st); rc != RT_OK) return rc;
         r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
         r->frames += 1;
         return RT_OK;
     }
-    FrameLaunch L{mode, md, tex, grid, block, lds, st, s->frame_waves};
+    FrameLaunch L{mode, md, tex, dim3((F.nunits + 3) / 4), dim3(256), stack_bytes(s), st, s->frame_waves};
     SceneView view = s->view;
     view.walk_stats = r->d_counters;
     view.walk_check = r->walk_check;
-    const uint64_t pkey = param_key(r, F, cam, p);
-    bool gate_open = false;
-    if (int rc = tune_gate(r, pkey, st, gate_open); rc != RT_OK) return rc;
+    FramePlan P;
+    P.key = param_key(r, F, cam, p);
+    if (int rc = tune_gate(r, P.key, st, P.gate_open); rc != RT_OK) return rc;
     // did the GPU run dry since the previous frame?  (a timed group then restarts: kTuneRestarts)
-    bool stalled = false;
-    if (r->stall_armed) {
-        stalled = hipEventQuery(r->stall_ev) == hipSuccess;
-        r->stall_armed = false;
-    }
-    // camera-ray walk (only the global-node primary+shadow kernel has both)
-    const bool walk_kernel = mode == RT_MODE_PATH && md == 1 && !s->ext;
-    int walk_ev0 = -1, walk_ev1 = -1;   // tev recorded before / after this launch
-    int cost_map = -1;                  // this frame records the tile costs under walk 0 / 1
-    bool walk_decided = false;
-    // the walk's timed groups (lane, wave, wave, lane) must all run on one parameter set's
-    // frames: a set change in the middle (a multi-GPU deal switch, a camera move) restarts them
-    if (walk_kernel && s->walk == RT_WALK_AUTO && r->tune >= 1 && r->tune < kTuneDecide && pkey != r->tune_key)
-        r->tune = 0;
-    if (r->tune == 0) {
-        r->tune_key = pkey;
-        r->walk_restarts = 0;
-        r->walk_rg = -1;
-    }
-    const bool walk_pending = walk_kernel && s->walk == RT_WALK_AUTO && r->tune < kTuneDone;
-    if (walk_kernel) {
-        if (s->walk == RT_WALK_WAVE) view.wave_primary = 1;
-        else if (s->walk == RT_WALK_AUTO && (gate_open || r->tune >= kTuneDecide)) {
-            if (r->tune < kTuneDecide) {
-                if (!r->tev[0])
-                    for (auto &e : r->tev) HIP_TRY(hipEventCreate(&e));
-                if (r->tune >= 1) {   // groups lane, wave, wave, lane
-                    if ((r->tune - 1) / kTuneGroup != r->walk_rg) {
-                        r->walk_rg = (r->tune - 1) / kTuneGroup;
-                        r->walk_restarts = 0;
-                    }
-                    if (stalled && (r->tune - 1) % kTuneGroup != 0 && r->walk_restarts < kTuneRestarts) {
-                        r->tune -= (r->tune - 1) % kTuneGroup;             // redo the group from its first frame
-                        ++r->walk_restarts;
-                    }
-                    const int g = (r->tune - 1) / kTuneGroup, i = (r->tune - 1) % kTuneGroup;
-                    view.wave_primary = (g == 1 || g == 2) ? 1 : 0;
-                    if (i == 0) walk_ev0 = 2 * g;
-                    if (i == kTuneGroup - 1) walk_ev1 = 2 * g + 1;
-                    if (i == 0 && g < 2) cost_map = g;   // each walk's tile costs, on its first frame
-                }
-                ++r->tune;
-            } else if (r->tune == kTuneDecide) {                   // decide once, after the timed groups
-                float t[4] = {};
-                HIP_TRY(hipEventSynchronize(r->tev[7]));
-                for (int g = 0; g < 4; ++g) HIP_TRY(hipEventElapsedTime(&t[g], r->tev[2 * g], r->tev[2 * g + 1]));
-                r->wave = tuned_alternative(t);
-                r->tune = kTuneDone;
-                walk_decided = true;
-            }
-            if (r->tune == kTuneDone) view.wave_primary = r->wave ? 1 : 0;
-        }
-    }
-    int split_ev0 = -1, split_ev1 = -1;   // sev recorded before / after this launch
+    P.stalled = r->stall_armed && hipEventQuery(r->stall_ev) == hipSuccess;
+    r->stall_armed = false;
+    const bool ps_kernel = mode == RT_MODE_PATH && md == 1;   // the primary+shadow frame kernel
+    if (int rc = walk_step(r, ps_kernel && !s->ext, view, P); rc != RT_OK) return rc;
     if (s->tile_order) {
         // half-tile units: primary+shadow frames of the global-node kernel, whole-tile units only
-        const bool split_ok = mode == RT_MODE_PATH && md == 1 && F.nchunks <= 1;
-        const int rc = tile_order_step(r, F, pkey, cost_map >= 0 ? cost_map : walk_decided ? 2 : walk_pending ? 3 : -1,
-                                       split_ok, gate_open, stalled, split_ev0, split_ev1);
-        if (rc != RT_OK) return rc;
+        if (int rc = tile_order_step(r, F, ps_kernel && F.nchunks <= 1, P); rc != RT_OK) return rc;
         L.grid = dim3((F.nunits + 3) / 4);
     }
-    // Overlapped primary+shadow frames: each pixel's accumulator update has to follow the
-    // previous frame's, but its traversal does not.  Once the frame is in its steady state
-    // (no timing events, no cost recording) the frame kernel runs on one of the renderer's
-    // two overlap streams (by frame parity) and stores its samples in the frame-level result
-    // buffer of that parity; a finishing pass on the caller's stream then does the running
-    // average + RGB8 (k_pt_finish, the same float operations as the kernel's own epilogue).
-    // Frame f+1's waves so fill the CUs that frame f's tail leaves idle.  The kernel touches
-    // only renderer-private memory; a stream waits only for the finishing pass that last read
-    // its result buffer (two frames back).
-    // Three result buffers (RT_PS_BUFFERS): with two, frame f + 2's kernel waited for frame f's
-    // finishing pass while frame f + 1's kernel shared the CUs, which put the finishing pass and
-    // two cross-stream waits on the critical path (TEAPOT-F 1080p 0.119 ms per frame vs 0.1055
-    // with three; four measure the same as three; profiles/r02/ps_window*.log).
-    // It pays where a frame is latency- or tail-bound (mig29 x16 1080p 0.41 -> 0.33 ms, 720p
-    // 0.385 -> 0.255 ms) and costs where it is issue-bound (TEAPOT-F 1080p 0.1024 -> 0.1055 ms:
-    // the finishing pass's extra 66 MB of sample traffic is not hidden there), and only
-    // when the caller submits frames back to back.  A small frame -- a multi-GPU rank's 1/N
-    // shard, about one round of resident waves -- is one latency chain long, and more frames
-    // in flight keep filling its idle issue slots: up to 6 renderer streams (round 3).  So by
-    // default each renderer times serial, 2, 4 and 6 frames in flight on its own frames and
-    // keeps the fastest (RT_PS_PIPELINE: -1 auto, 0 off, 1 on with RT_PS_DEPTH frames in flight).
     const uint64_t ps_bytes = (uint64_t)p->spp * F.ntiles_local * 64u * 16u;
     // (sample-split frames -- a multi-GPU rank's shard at spp N -- store their samples anyway;
     // overlapped, they go to the result buffers instead of d_samples)
-    const bool ps_ok = s->ps_pipeline != 0 && mode == RT_MODE_PATH && md == 1 &&
-                       split_ev0 < 0 && split_ev1 < 0 && r->split_phase < 0 && !F.tile_cost && !walk_pending &&
+    const bool ps_ok = s->ps_pipeline != 0 && ps_kernel && !r->split_tg.active() && !F.tile_cost && !P.walk_pending &&
                        ps_bytes <= (2ull << 30);
-    // frames in flight for this frame: 0 = serial, else 2..6 renderer streams
-    uint32_t depth_k = (ps_ok && s->ps_pipeline == 1) ? s->ps_depth : 0u;
-    // pev recorded on the caller's stream after this frame: ps_ev0 after a timed group's frame
-    // SKIP, ps_ev1 after its last -- the group is timed from one frame's completion to another's,
-    // G - 1 - SKIP frame periods at its depth in steady state.  (Events before the first frame timed a
-    // deeper group short: its first kernels start on their streams while the caller's stream still
-    // finishes earlier frames; TEAPOT-F shards then picked 4-6 in flight, 0.125-0.144 ms against
-    // 0.092 with 2.  Round 4.)
-    int ps_ev0 = -1, ps_ev1 = -1;
-    // More than 2 frames in flight are candidates only for frames of a few rounds of resident
-    // waves (a multi-GPU rank's small shard, 720p) or whose costliest tile outlasts twice the
-    // frame's throughput time (tail_bound, from the tile-order cost map: mig29 x16 1080p and its
-    // 1/2 shard, 16,200 tiles, 0.222 -> 0.167 ms with 4 in flight; round 4, depth_exp_*.jsonl);
-    // a throughput-bound frame (TEAPOT-F 1080p, 8 rounds) lost with 4 (0.1035 -> 0.114 ms) and
-    // the timing only risked picking them.  Groups in palindromic order: serial, 2, 4, 6, 6, 4,
-    // 2, serial -- or serial, 2, 2, serial.
-    const bool deep_ok = F.nunits <= 3u * 4u * 5u * s->num_cus || r->tail_bound;
-    static const uint32_t kDeep[8] = {0, 2, 4, 6, 6, 4, 2, 0}, kShallow[4] = {0, 2, 2, 0};
-    if (ps_ok && s->ps_pipeline < 0 && !gate_open) depth_k = 0;   // timing not started: serial
-    if (ps_ok && s->ps_pipeline < 0 && gate_open) {
-        if (r->ps_phase == 0) r->ps_groups = deep_ok ? 8 : 4;
-        const int NG = r->ps_groups;
-        // a group's first frames fill its pipeline (every renderer stream starts behind the previous
-        // group), and their completions bunch up: timed from the first frame's completion, a 6-deep
-        // group of 16 frames measured 0.23-0.25 ms per frame on mig29 x16 whose 6-deep frames then
-        // ran at 0.272 ms against 0.256 with 4 (round 5).  Deep timings run 32-frame groups and time
-        // them from the completion of frame 8 (23 periods), shallow ones 16 frames from frame 2.
-        const int G = NG == 8 ? 2 * kPsGroup : kPsGroup, SKIP = NG == 8 ? 8 : 2;
-        const uint32_t *depths = NG == 8 ? kDeep : kShallow;
-        if (r->ps_phase > 0 && r->ps_phase < NG * G && r->frames != r->ps_last + 1) {   // interrupted
-            r->ps_phase = 0;
-            r->ps_restarts = 0;
-        r->ps_rg = -1;
-        }
-        if (r->ps_phase > 0 && r->ps_phase == NG * G) {
-            HIP_TRY(hipEventSynchronize(r->pev[2 * NG - 1]));
-            for (int g = 0; g < NG; ++g) HIP_TRY(hipEventElapsedTime(&r->ps_ms[g], r->pev[2 * g], r->pev[2 * g + 1]));
-            // group g and its mirror NG - 1 - g ran the same depth.  Shallow candidates (serial,
-            // 2): 2 in flight replaces serial only when it beats it by kTuneMargin, so noise does not
-            // buy frames in flight.  Deep candidates (tail-bound or small frames: serial, 2, 4, 6):
-            // 4 in flight is the default, which another depth replaces only when it beats it by
-            // kTuneMargin -- the deep groups time a deeper pipeline's gain short (mig29 x16: 4 in
-            // flight 1.9 % ahead of 2 in its groups, 3.5 % ahead in steady state, 0.236-0.238
-            // against 0.246 ms; profiles/r05/c4depth), so with serial as the default the choice
-            // between 2 and 4 was a coin toss
-            const int pref = NG == 8 ? 2 : 0;
-            float best = r->ps_ms[pref] + r->ps_ms[NG - 1 - pref];
-            r->ps_use = depths[pref];
-            for (int g = 0; g < NG / 2; ++g) {
-                if (g == pref) continue;
-                const float t = r->ps_ms[g] + r->ps_ms[NG - 1 - g];
-                if (t < best * (1.0f - kTuneMargin)) { best = t; r->ps_use = depths[g]; }
-            }
-            r->ps_phase = -1;
-            // every timed frame's finishing pass preceded pev[2 NG - 1]: no buffer is in use, and
-            // the ones the chosen depth never touches are released (a 1080p spp-1 buffer is 33 MB)
-            const uint32_t keep = r->ps_use == 0 ? 0u : (s->ps_buffers ? s->ps_buffers : r->ps_use + 1u);
-            for (uint32_t b = keep; b <= (uint32_t)kPsMaxDepth; ++b) {
-                if (r->ps_res[b]) HIP_TRY(hipFree(r->ps_res[b]));
-                r->ps_res[b] = nullptr;
-                r->ps_res_bytes[b] = 0;
-                r->ps_fin_set[b] = false;
-            }
-        }
-        if (r->ps_phase >= 0) {
-            if (r->ps_phase == 0) {   // streams, events and every result buffer before the timing
-                if (!r->pev[0])
-                    for (auto &e : r->pev) HIP_TRY(hipEventCreate(&e));
-                const uint32_t maxd = NG == 8 ? 6u : 2u;
-                int rc = ensure_pipe_streams(r, (int)maxd);
-                const uint32_t nb = s->ps_buffers ? s->ps_buffers : maxd + 1u;
-                for (uint32_t k = 0; k < nb && rc == RT_OK; ++k) rc = ensure_ps_res(r, k, ps_bytes);
-                if (rc != RT_OK) return rc;
-            }
-            if (r->ps_phase / G != r->ps_rg) {
-                r->ps_rg = r->ps_phase / G;
-                r->ps_restarts = 0;
-            }
-            if (stalled && r->ps_phase % G != 0 && r->ps_restarts < kTuneRestarts) {
-                r->ps_phase -= r->ps_phase % G;                                // redo the group
-                ++r->ps_restarts;
-            }
-            const int g = r->ps_phase / G;
-            depth_k = depths[g];
-            if (r->ps_phase % G == SKIP) ps_ev0 = 2 * g;
-            if (r->ps_phase % G == G - 1) ps_ev1 = 2 * g + 1;
-            r->ps_last = r->frames;
-            ++r->ps_phase;
-        } else {
-            depth_k = r->ps_use;
-        }
-    }
-    const bool ps_pipe = depth_k > 0;
-
-    uint32_t buf = 0;
-    int lane_st = 0;
-    if (ps_pipe) {
-        int rc = ensure_pipe_streams(r, (int)depth_k);
-        if (rc != RT_OK) return rc;
-        // frame n's kernel on renderer stream n % depth, its samples in buffer n % buffers: with
-        // depth + 1 buffers frame n + depth + 1 waits for frame n's finishing pass only, which
-        // follows frame n's kernel alone -- never a kernel still running beside it
-        const uint32_t buffers = s->ps_buffers ? s->ps_buffers : depth_k + 1u;
-        buf = r->ps_count % buffers;
-        lane_st = (int)(r->ps_count % depth_k);
-        ++r->ps_count;
-        if ((rc = ensure_ps_res(r, buf, ps_bytes)) != RT_OK) return rc;
-        L.stream = r->pt_stream[lane_st];
-        if (r->ps_fin_set[buf]) HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_fin[buf], 0));
-        if (!r->ps_prev || ps_ev0 >= 0) {
-            // switching from serial frames: start behind the caller's stream; a timed group's first
-            // frame: every renderer stream starts behind everything before it, so that no frame of
-            // the group runs beside the previous group's (whose depth differs)
-            if (!r->ps_join) HIP_TRY(hipEventCreateWithFlags(&r->ps_join, hipEventDisableTiming | hipEventReleaseToDevice));
-            HIP_TRY(hipEventRecord(r->ps_join, st));
-            if (ps_ev0 >= 0)
-                for (int k = 0; k < r->nstreams; ++k) HIP_TRY(hipStreamWaitEvent(r->pt_stream[k], r->ps_join, 0));
-            else
-                HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_join, 0));
-        }
-        F.samples = r->ps_res[buf];
-    }
-    if (ps_ok) r->ps_prev = depth_k;
+    if (int rc = overlap_step(r, F, L, ps_ok, ps_bytes, st, P); rc != RT_OK) return rc;
     L.lds_bytes = stack_bytes(s) + walk_bytes(s, view);   // the camera walk's word stack when it runs
-    frame_build(r, view, F, L, ps_pipe);
-    if (walk_ev0 >= 0) HIP_TRY(hipEventRecord(r->tev[walk_ev0], st));
-    if (split_ev0 >= 0) HIP_TRY(hipEventRecord(r->sev[split_ev0], st));
-    if (s->ext) kext::launch_frame(view, F, L);
-    else kcore::launch_frame(view, F, L);
-    HIP_TRY(hipGetLastError());
-    if (walk_ev1 >= 0) HIP_TRY(hipEventRecord(r->tev[walk_ev1], st));
-    if (split_ev1 >= 0) HIP_TRY(hipEventRecord(r->sev[split_ev1], st));
-    if (ps_pipe) {
-        HIP_TRY(hipEventRecord(r->pt_lv[lane_st], L.stream));
-        HIP_TRY(hipStreamWaitEvent(st, r->pt_lv[lane_st], 0));
-    }
-    if (F.samples) {   // the pixels' samples in sample order, running average, RGB8
-        PathArgs P{};
-        P.batch_spp = p->spp;
-        P.result = F.samples;
-        if (s->ext) kext::launch_pt_finish(F, P, true, st);
-        else kcore::launch_pt_finish(F, P, true, st);
-        HIP_TRY(hipGetLastError());
-        if (ps_pipe) {
-            HIP_TRY(hipEventRecord(r->ps_fin[buf], st));
-            r->ps_fin_set[buf] = true;
-        }
-    }
-    if (ps_ev0 >= 0) HIP_TRY(hipEventRecord(r->pev[ps_ev0], st));
-    if (ps_ev1 >= 0) HIP_TRY(hipEventRecord(r->pev[ps_ev1], st));
-    // a timed group is running: mark this frame's completion for the next submission's stall check
-    if ((r->tune >= 1 && r->tune < kTuneDecide) || r->split_phase >= 0 || (s->ps_pipeline < 0 && r->ps_phase > 0)) {
-        if (!r->stall_ev) HIP_TRY(hipEventCreateWithFlags(&r->stall_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(r->stall_ev, st));
-        r->stall_armed = true;
-    }
-    (void)tiles_y;
+    frame_build(r, view, F, L, P.depth > 0);
+    if (int rc = submit_frame(r, view, F, L, P, st); rc != RT_OK) return rc;
     r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
     r->frames += 1;
     return RT_OK;
@@ -2267,6 +2164,7 @@ int rt_renderer_create(rt_scene *s, uint32_t W, uint32_t H, rt_renderer **out) {
     r->scene = s;
     r->device = s->device;
     r->W = W; r->H = H;
+    start_two_way(r->walk_tg, true);
     hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&r->d_acc, sizeof(float4) * (size_t)W * H);   // Renderer::Init, renderer.cpp:6-12
     if (e == hipSuccess) e = hipMemsetAsync(r->d_acc, 0, sizeof(float4) * (size_t)W * H, r->stream);
@@ -2310,14 +2208,9 @@ int rt_renderer_destroy(rt_renderer *r) {
     if (r->d_map) (void)hipFree(r->d_map);
     if (r->d_work) (void)hipFree(r->d_work);
     if (r->d_where) (void)hipFree(r->d_where);
-    for (auto &e : r->tev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : r->sev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : r->pev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : r->gate_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (auto &row : r->tune_ev)
+        for (auto &e : row)
+            if (e) (void)hipEventDestroy(e);
     if (r->ps_join) (void)hipEventDestroy(r->ps_join);
     if (r->cost_ev) (void)hipEventDestroy(r->cost_ev);
     if (r->stall_ev) (void)hipEventDestroy(r->stall_ev);
@@ -2456,7 +2349,7 @@ int rt_renderer_overlap(const rt_renderer *r, int *state, float ms[4]) {
     rt_renderer_overlap_depth(r, &depth, all);
     *state = depth < 0 ? -1 : (depth > 1 ? 1 : 0);
     if (ms) {   // serial, 2 in flight, 2 in flight, serial
-        const int n = r->ps_groups == 8 ? 8 : 4;
+        const int n = r->ps_tg.groups == 8 ? 8 : 4;
         const int g[4] = {0, 1, n - 2, n - 1};
         for (int k = 0; k < 4; ++k) ms[k] = all[g[k]];
     }
@@ -2466,15 +2359,12 @@ int rt_renderer_overlap(const rt_renderer *r, int *state, float ms[4]) {
 int rt_renderer_choices(const rt_renderer *r, int *walk, int *split, float walk_ms[4], float split_ms[4]) {
     if (!r || !walk || !split) return fail(RT_ERR_INVALID, "rt_renderer_choices: null argument");
     const rt_scene *s = r->scene;
-    *walk = s->walk == RT_WALK_WAVE ? 1 : s->walk == RT_WALK_LANE ? 0 : (r->tune == kTuneDone ? (r->wave ? 1 : 0) : -1);
-    *split = r->order_state == 2 && r->split_phase < 0 ? (r->use_split ? 1 : 0) : -1;
+    const bool split_set = r->order_state == 2 && !r->split_tg.active();
+    *walk = s->walk == RT_WALK_WAVE ? 1 : s->walk == RT_WALK_LANE ? 0 : r->wave;
+    *split = split_set ? (r->use_split ? 1 : 0) : -1;
     for (int g = 0; g < 4; ++g) {
-        float t = 0.0f;
-        if (walk_ms) {
-            if (r->tune == kTuneDone && s->walk == RT_WALK_AUTO && r->tev[2 * g]) (void)hipEventElapsedTime(&t, r->tev[2 * g], r->tev[2 * g + 1]);
-            walk_ms[g] = t;
-        }
-        if (split_ms) split_ms[g] = (r->split_phase < 0 && r->order_state == 2) ? r->split_ms[g] : 0.0f;
+        if (walk_ms) walk_ms[g] = (r->wave >= 0 && s->walk == RT_WALK_AUTO) ? r->walk_ms[g] : 0.0f;
+        if (split_ms) split_ms[g] = split_set ? r->split_ms[g] : 0.0f;
     }
     return RT_OK;
 }
@@ -2482,12 +2372,12 @@ int rt_renderer_choices(const rt_renderer *r, int *walk, int *split, float walk_
 int rt_renderer_overlap_depth(const rt_renderer *r, int *depth, float ms[8]) {
     if (!r || !depth) return fail(RT_ERR_INVALID, "rt_renderer_overlap_depth: null argument");
     const int32_t mode = r->scene->ps_pipeline;
-    const bool decided = mode < 0 && r->ps_phase == -1;
+    const bool decided = mode < 0 && r->ps_use >= 0;
     if (mode == 0) *depth = 1;
     else if (mode == 1) *depth = (int)r->scene->ps_depth;
-    else *depth = decided ? (r->ps_use ? (int)r->ps_use : 1) : -1;
+    else *depth = decided ? (r->ps_use ? r->ps_use : 1) : -1;
     if (ms)
-        for (int g = 0; g < 8; ++g) ms[g] = (decided && g < r->ps_groups) ? r->ps_ms[g] : 0.0f;
+        for (int g = 0; g < 8; ++g) ms[g] = (decided && g < r->ps_tg.groups) ? r->ps_ms[g] : 0.0f;
     return RT_OK;
 }
 
