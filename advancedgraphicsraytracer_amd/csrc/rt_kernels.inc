@@ -65,12 +65,6 @@ __device__ __forceinline__ float cr_atan2(float y, float x) { return (float)atan
 __device__ __forceinline__ float cr_acos(float x) { return (float)acos((double)x); }
 __device__ __forceinline__ float cr_asin(float x) { return (float)asin((double)x); }
 
-// float -> uint the way the reference's x86-64 build converts: (uint32)(int64)trunc(f)
-__device__ __forceinline__ uint32_t f2u_wrap(float f) {
-    if (!(f == f) || f >= 9.2e18f || f <= -9.2e18f) return 0u;
-    return (uint32_t)(long long)f;
-}
-
 // ------------------------------------------------------------------ slab tests (scene.h:414-450)
 // EXACT: the reference's std::min/std::max selects, NaN behaviour included.
 // FAST (chosen per wave when every active ray has a finite origin and finite 1/D and the
@@ -1329,10 +1323,18 @@ __device__ __forceinline__ uint32_t global_tile(const FrameArgs &F, uint32_t loc
 }
 
 // the wave's shadow / bounce ray counts into counter slot `wave` (kCounterSlots)
+// BINARY: every lane's shadow count is 0 or 1 and no lane bounces (one sample at Trace depth 1), so
+// the wave's count is a ballot's popcount instead of wave_sum's six dependent LDS round trips
+template <bool BINARY = false>
 __device__ __forceinline__ void count_rays(const FrameArgs &F, uint32_t wave, uint32_t lane, uint32_t nshadow,
                                            uint32_t nbounce) {
-    nshadow = wave_sum(nshadow);
-    nbounce = wave_sum(nbounce);
+    if constexpr (BINARY) {
+        nshadow = (uint32_t)__popcll(__ballot(nshadow != 0u));
+        nbounce = 0u;
+    } else {
+        nshadow = wave_sum(nshadow);
+        nbounce = wave_sum(nbounce);
+    }
     if (lane == 0) {
         unsigned long long *c = F.counters + (size_t)(wave % kCounterSlots) * 8u;
         if (nshadow) atomicAdd(&c[0], (unsigned long long)nshadow);
@@ -1418,7 +1420,7 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
             F.out[px] = rgb;
         }
     }
-    count_rays(F, unit, lane, nshadow, nbounce);
+    count_rays<MODE == M_PATH && MAXD == 1 && ONE>(F, unit, lane, nshadow, nbounce);
     if (F.tile_cost && lane == 0) F.tile_cost[local_tile] = (uint32_t)(__builtin_amdgcn_s_memtime() - t_start);
 }
 
@@ -1439,8 +1441,17 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES_PER_SIMD) void k_render(SceneV
 // sample chunks): render_tile without the sample loop and its running sum, which the plain build
 // carries across the traversal -- 51 VGPRs instead of 71, no spill, so 8 waves/SIMD where the LDS
 // stacks allow (TEAPOT-F 1080p serial 0.1025 -> 0.096 ms).  Round 4; frame_build picks it.
+// The two argument records (about 110 dwords) are read where they are used, from the kernel-
+// argument segment: named as parameters they are all loaded at entry, more scalars than the
+// kernel has registers for, and the compiler parked them in the lanes of a VGPR (42 v_writelane /
+// 70 v_readlane, which issue as VALU).  Read in place, the traversal's fields are loaded before
+// its loops and the shading / epilogue fields after them.
+struct FrameKernArgs { SceneView S; FrameArgs F; };   // the segment's layout of (SceneView, FrameArgs)
 template <bool TEX_SKY>
-__global__ __launch_bounds__(256, 8) void k_render_w8(SceneView S, FrameArgs F) {
+__global__ __launch_bounds__(256, 8) void k_render_w8(SceneView, FrameArgs) {
+    const auto *ka = (const FrameKernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    const SceneView &S = ka->S;
+    const FrameArgs &F = ka->F;
     extern __shared__ uint32_t lds_stack[];
     const uint32_t tid = threadIdx.x;
     const uint32_t unit = blockIdx.x * 4u + (tid >> 6);
