@@ -9,7 +9,8 @@
 // wave64s, one wave per 8x8 screen tile (the reference's PACKET_SIZE 64 / SQRT_PACKET_SIZE 8,
 // Ray.h:3-5), one lane per pixel.  No MFMA: this is branchy scalar fp32.
 //
-// Device scene layout in HBM (built once by rt_scene_create):
+// Device scene layout in HBM (packed by pack_scene, rt_scene_pack.cpp, with the encoders of
+// rt_records.h; uploaded once by rt_scene_create):
 //   nodes  : the reference's 32-byte BVHNode array (root 0, node 1 unused, sibling pairs
 //            64-byte aligned) with (leftFirst, count) replaced by one packed word
 //            (leftFirst << 8 | count) so a 64-byte sibling-pair load carries everything
@@ -32,10 +33,9 @@
 
 #include "rt_dev_types.h"
 #include "rt_internal.h"
+#include "rt_records.h"
 #include "rt_refit.h"
 #include "rt_tune.h"
-
-
 
 // ====================================================================== host side
 using namespace rt;
@@ -49,16 +49,6 @@ using namespace rt;
                         std::string(#expr) + ": " + hipGetErrorString(e_));                   \
     } while (0)
 
-// RT_PT_QUADS=1: the lane kernel walks two-level node records (build_quads).  Exact (the GPU suite
-// passes with it on; test_wavefront_equals_one_kernel_path_tracer runs it), but measured slower,
-// so off by default (tools/ab.py serial frames, profiles/r05/quadab): CFG3-sub 2.133 -> 2.385 ms,
-// CFG5-sub 8.49 -> 9.41, TEAPOT-F depth 10 1.150 -> 1.253, mig29 x16 spp 4 depth 4 3.78 -> 4.40 --
-// a record step costs four slab tests, two box unions and a 128-B load for every lane of the
-// wave whichever branch (leaf, odd half, record) each lane is in, and the lanes' chains shrink less
-// than the step grows.
-#ifndef RT_PT_QUADS_DEFAULT
-#define RT_PT_QUADS_DEFAULT 0
-#endif
 struct rt_scene {
     int device = 0;
     SceneView view{};
@@ -254,137 +244,7 @@ struct rt_renderer {
 
 namespace {
 
-inline float ubits(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-inline float ibits(int32_t i) { float f; std::memcpy(&f, &i, 4); return f; }
-
 enum { kWalk, kSplit, kOverlap, kGate };   // rt_renderer::tune_ev rows
-
-// LDS stack entries per lane: a traversal pushes at most one entry per tree level, so the tree
-// depth is enough.  Rounding it up to 8 cost occupancy where the stacks bound the workgroups
-// per CU (mig29 x16: 26 levels, 32 KB per workgroup -> 5 per CU; exact: 26 KB -> 6): CFG3-sub
-// 1.79 -> 1.65 ms, CFG5-sub 7.58 -> 7.47 ms, mig29 x16 0.330 -> 0.321 ms, TEAPOT-F unchanged
-// (round 3, profiles/r03/ab_stack/).
-#ifndef RT_STACK_ROUND
-#define RT_STACK_ROUND 1u
-#endif
-// Two-level node records (the path tracer's lane kernel, k_pt_lanes<.., true>): one 128-B
-// record per interior node x at even depth (the root at 0) holding the node entries of x's
-// grandchildren -- slots 2h, 2h+1 = the children of x's child h -- or, for a leaf child h, that
-// leaf's own entry in slot 2h (flag bit 0 in its .w word).  One load then serves two binary
-// levels: the walk tests x's children on boxes rebuilt as the union of their children's (the
-// reference's node bounds ARE that union -- each node's box is the min / max over its primitives'
-// bounds, Scene::UpdateNodeBounds, template/scene.h:855-865 -- checked bit for bit here), then
-// the nearer child's children on their own entries, in the reference's order and against the
-// same r.t: the visits are the binary walk's exactly.  A popped odd-depth child is addressed by
-// (its parent's record, half) and reads its children pair from that record.  Entry words: leaf
-// (leftFirst << 8 | count) as in the binary array, even-depth interior node (record << 8), odd
-// marker ((kQuadOdd | record << 1 | half) << 8).  false (no records) when a box is NaN, a parent is
-// not the exact union of its children (a caller's prebuilt tree), or the tree is too large.
-constexpr uint32_t kQuadOdd = 1u << 23;
-bool build_quads(const Bvh &b, const std::vector<uint8_t> &sticky, std::vector<float4> &rec, uint32_t &root_word) {
-    const Node *N = b.nodes.data();
-    if (b.nodes_used < 3 || N[0].count > 0) return false;
-    std::vector<int32_t> id(b.nodes_used, -1);
-    std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}};
-    std::vector<uint32_t> order;
-    while (!st.empty()) {   // pre-order, even-depth interior nodes numbered as met
-        auto [k, d] = st.back();
-        st.pop_back();
-        const Node &nd = N[k];
-        if (nd.count > 0) continue;
-        if (!(d & 1u)) { id[k] = (int32_t)order.size(); order.push_back(k); }
-        st.push_back({nd.leftFirst + 1, d + 1});
-        st.push_back({nd.leftFirst, d + 1});
-    }
-    if (order.size() >= (kQuadOdd >> 1)) return false;
-    auto bits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-    // the union of two floats as the device's fminf / fmaxf gives it, or fail on NaN / +-0 ties
-    auto pick = [&](float a, float c, bool mn, float want) {
-        if (a != a || c != c || want != want) return false;
-        if (a == c && bits(a) != bits(c)) return false;
-        const float u = mn ? (a < c ? a : c) : (a > c ? a : c);
-        return bits(u) == bits(want);
-    };
-    auto entry = [&](uint32_t g, float4 *q) {
-        const Node &nd = N[g];
-        const uint32_t w = nd.count > 0 ? ((nd.leftFirst << 8) | nd.count) : ((uint32_t)id[g] << 8);
-        q[0] = make_float4(nd.mn[0], nd.mn[1], nd.mn[2], nd.mx[0]);
-        q[1] = make_float4(nd.mx[1], nd.mx[2], ubits(w), 0.0f);
-    };
-    // the .w word of each entry: bit 0 (first slot of a half) the child is a leaf and this its entry,
-    // bit 1 this entry's node is sticky (mark_sticky), bit 2 (first slot) the child itself is sticky
-    rec.assign(8 * order.size(), make_float4(0, 0, 0, 0));
-    for (size_t r = 0; r < order.size(); ++r) {
-        const Node &x = N[order[r]];
-        for (uint32_t h = 0; h < 2; ++h) {
-            const uint32_t c = x.leftFirst + h;
-            float4 *q = &rec[8 * r + 4 * h];
-            const Node &cn = N[c];
-            const uint32_t sc = sticky[c] ? 6u : 0u;
-            if (cn.count > 0) {
-                entry(c, q);
-                q[1].w = ubits(1u | sc);
-                continue;
-            }
-            const Node &g1 = N[cn.leftFirst], &g2 = N[cn.leftFirst + 1];
-            for (int a = 0; a < 3; ++a)
-                if (!pick(g1.mn[a], g2.mn[a], true, cn.mn[a]) || !pick(g1.mx[a], g2.mx[a], false, cn.mx[a])) return false;
-            entry(cn.leftFirst, q);
-            entry(cn.leftFirst + 1, q + 2);
-            q[1].w = ubits((sticky[cn.leftFirst] ? 2u : 0u) | (sc & 4u));
-            q[3].w = ubits(sticky[cn.leftFirst + 1] ? 2u : 0u);
-        }
-    }
-    root_word = (uint32_t)id[0] << 8;
-    return true;
-}
-
-uint32_t pick_stack(uint32_t depth) {   // entries needed <= tree depth (rounded up to RT_STACK_ROUND)
-    uint32_t need = depth < 2 ? 2 : depth;
-    return (need + RT_STACK_ROUND - 1u) / RT_STACK_ROUND * RT_STACK_ROUND;
-}
-
-int material_flag(const rt_material &m, float diffuse, float specular) {   // getFlag overrides
-    switch (m.kind) {
-    case RT_DIFFUSE: return F_DIFFUSE;
-    case RT_MIRROR: return F_SPECULAR;
-    case RT_DIELECTRIC: return F_DIELECTRIC;
-    case RT_LIGHT: return F_LIGHT;
-    default:
-        if (diffuse < kFLT_EPSILON) return F_SPECULAR;
-        if (specular < kFLT_EPSILON) return F_DIFFUSE;
-        return F_MIX;
-    }
-}
-
-constexpr uint32_t kMaxNodes = 1u << 24;   // the packed word's leftFirst field is 24 bits wide
-
-int validate_bvh(const Bvh &b, uint32_t n) {
-    if (b.nodes_used < 2 || b.nodes_used > b.nodes.size()) return fail(RT_ERR_INVALID, "BVH node count out of range");
-    std::vector<uint8_t> seen(n, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (b.indices[i] >= n || seen[b.indices[i]]) return fail(RT_ERR_INVALID, "BVH indices are not a permutation");
-        seen[b.indices[i]] = 1;
-    }
-    // walk from the root: children in range, leaves inside the index array
-    std::vector<uint32_t> st{0};
-    size_t visits = 0;
-    while (!st.empty()) {
-        uint32_t k = st.back();
-        st.pop_back();
-        if (++visits > 2 * (size_t)b.nodes_used) return fail(RT_ERR_INVALID, "BVH has a cycle");
-        const Node &nd = b.nodes[k];
-        if (nd.count > 0) {
-            if ((uint64_t)nd.leftFirst + nd.count > n) return fail(RT_ERR_INVALID, "BVH leaf outside the index array");
-            continue;
-        }
-        if (nd.leftFirst < 2 || nd.leftFirst + 1 >= b.nodes_used || (nd.leftFirst & 1u))
-            return fail(RT_ERR_INVALID, "BVH child pair out of range / misaligned");
-        st.push_back(nd.leftFirst);
-        st.push_back(nd.leftFirst + 1);
-    }
-    return RT_OK;
-}
 
 void free_scene(rt_scene *s) {
     if (!s) return;
@@ -414,366 +274,36 @@ int ensure_device(int device) {
     return RT_OK;
 }
 
-inline f3 tvec_host(float4 r0, float4 r1, float4 r2, f3 a) {
-    const float M[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
-    return tvec(M, a);
-}
-
-// The wave camera walk's sticky boxes (rt_kernels.inc, wave_closest_hit_fast): a node with a
-// primitive below it whose computed t can lie well before its leaf box's entry -- a sliver
-// triangle (its smallest corner angle's sine under 2^RT_WALK_STICKY, default 2^-8: the common
-// denominator of t, u, v is then mostly rounding, Primitive.h:255-273), a sphere (t = -b - sqrt(d)
-// near a tangent, Primitive.h:150-177) or a quad -- gets b.w = 1, and the walk culls it only on a
-// slab miss.  Computed in double on the float vertices.  b.w then holds the walk's cull margin per
-// node: `margin` (SceneView::walk_margin), +inf for a sticky node; the lane traversals never read it.
-void mark_sticky(const Bvh &b, const rt_scene_desc *d, std::vector<float4> &nodes, std::vector<uint8_t> &sticky,
-                 float margin, std::vector<uint8_t> &prim_flag, double &sliver_lim) {
-    double lim = std::ldexp(1.0, -8);
-    if (const char *e = std::getenv("RT_WALK_STICKY")) lim = std::atoi(e) >= 0 ? 0.0 : std::ldexp(1.0, std::atoi(e));
-    bool spheres = true;   // RT_WALK_STICKY_SPHERES=0: A/B only
-    if (const char *e = std::getenv("RT_WALK_STICKY_SPHERES")) spheres = std::atoi(e) != 0;
-    auto prim_sticky = [&](const rt_prim &p) {
-        if (p.type == RT_SPHERE || p.type == RT_QUAD) return spheres;
-        if (p.type != RT_TRIANGLE) return false;   // planes: an unbounded box, entered from inside
-        double v[3][3], e[3][3], len[3];
-        for (int k = 0; k < 3; ++k)
-            for (int a = 0; a < 3; ++a) v[k][a] = p.v[3 * k + a];
-        for (int k = 0; k < 3; ++k) {
-            for (int a = 0; a < 3; ++a) e[k][a] = v[(k + 1) % 3][a] - v[k][a];
-            len[k] = std::sqrt(e[k][0] * e[k][0] + e[k][1] * e[k][1] + e[k][2] * e[k][2]);
-        }
-        const double cx = e[0][1] * e[2][2] - e[0][2] * e[2][1], cy = e[0][2] * e[2][0] - e[0][0] * e[2][2],
-                     cz = e[0][0] * e[2][1] - e[0][1] * e[2][0];
-        const double area2 = std::sqrt(cx * cx + cy * cy + cz * cz);
-        std::sort(len, len + 3);
-        return !(area2 >= lim * len[1] * len[2]);   // sine of the smallest angle = 2 area / (two longest edges)
-    };
-    sliver_lim = lim;
-    prim_flag.resize(d->num_prims);
-    for (uint32_t i = 0; i < d->num_prims; ++i) prim_flag[i] = prim_sticky(d->prims[i]) ? 1 : 0;
-    const uint32_t used = b.nodes_used;
-    std::vector<uint32_t> parent(used, ~0u);
-    for (uint32_t i = 0; i < used; ++i)
-        if (i != 1 && b.nodes[i].count == 0)
-            for (uint32_t c = b.nodes[i].leftFirst; c < b.nodes[i].leftFirst + 2; ++c) parent[c] = i;
-    for (uint32_t i = 0; i < used; ++i) {
-        const Node &nd = b.nodes[i];
-        if (i == 1 || nd.count == 0 || nodes[2 * i + 1].w != 0.0f) continue;
-        bool st = false;
-        for (uint32_t k = nd.leftFirst; k < nd.leftFirst + nd.count && !st; ++k) st = prim_flag[b.indices[k]] != 0;
-        for (uint32_t j = i; st && j != ~0u && nodes[2 * j + 1].w == 0.0f; j = parent[j]) nodes[2 * j + 1].w = 1.0f;
-    }
-    sticky.assign(used, 0);
-    for (uint32_t i = 0; i < used; ++i) {
-        sticky[i] = nodes[2 * i + 1].w != 0.0f;
-        nodes[2 * i + 1].w = sticky[i] ? HUGE_VALF : margin;
-    }
-}
-
-int scene_create(const rt_scene_desc *d, rt_scene **out) {
-    if (!d || !out || !d->prims || d->num_prims == 0 || !d->materials || d->num_materials == 0)
-        return fail(RT_ERR_INVALID, "rt_scene_create: empty or null description");
-    *out = nullptr;
-    const uint32_t n = d->num_prims;
-    if (n >= (1u << 24)) return fail(RT_ERR_UNSUPPORTED, "more than 2^24 primitives");
-    for (uint32_t i = 0; i < n; ++i) {
-        const rt_prim &p = d->prims[i];
-        if (p.type < RT_SPHERE || p.type > RT_TRIANGLE)
-            return fail(RT_ERR_INVALID, "primitive " + std::to_string(i) + ": unknown type");
-        if (p.material < 0 || (uint32_t)p.material >= d->num_materials)
-            return fail(RT_ERR_INVALID, "primitive " + std::to_string(i) + ": material out of range");
-    }
-    if (d->prims[0].type != RT_SPHERE && d->prims[0].type != RT_QUAD)
-        return fail(RT_ERR_UNSUPPORTED, "primitive 0 must be the light, a sphere or a quad (Scene::GetRandomLight returns 0)");
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const rt_material &m = d->materials[i];
-        if (m.kind < RT_DIFFUSE || m.kind > RT_TEXTURE) return fail(RT_ERR_INVALID, "unknown material kind");
-        if (m.kind == RT_TEXTURE && (m.texture < 0 || (uint32_t)m.texture >= d->num_textures || !d->textures))
-            return fail(RT_ERR_INVALID, "material " + std::to_string(i) + ": texture index out of range");
-    }
-    for (uint32_t i = 0; i < d->num_textures; ++i)
-        if (!d->textures[i].pixels || !d->textures[i].width || !d->textures[i].height)
-            return fail(RT_ERR_INVALID, "texture " + std::to_string(i) + " is empty");
-    bool ext = d->prims[0].type == RT_QUAD;
-    {
-        const int lk = d->materials[d->prims[0].material].kind;
-        ext = ext || !(lk == RT_LIGHT || lk == RT_DIFFUSE || lk == RT_MIRROR || lk == RT_DSMIX);
-    }
-    for (uint32_t i = 0; i < n && !ext; ++i) ext = d->prims[i].type == RT_CUBE || d->prims[i].type == RT_QUAD;
-    for (uint32_t i = 0; i < d->num_materials && !ext; ++i) ext = d->materials[i].kind == RT_TEXTURE;
-    if (d->sky_pixels) {
-        uint32_t w = d->sky_width, h = d->sky_height;
-        if (!w || !h || (w & (w - 1)) || (h & (h - 1)))
-            return fail(RT_ERR_INVALID, "sky texture must have power-of-two sides (renderer.h:18)");
-    }
-    // interior nodes store a node index in the 24-bit leftFirst field of the packed device
-    // word (leftFirst << 8 | count): trees with more than 2^24 nodes cannot be addressed
-    if (d->bvh_nodes && d->bvh_num_nodes > kMaxNodes)
-        return fail(RT_ERR_UNSUPPORTED, "prebuilt BVH with more than 2^24 nodes (24-bit child index)");
-    int32_t bvh_kind = d->bvh_kind;
-    if (bvh_kind != RT_BVH_PLAIN && bvh_kind != RT_BVH_SBVH) return fail(RT_ERR_INVALID, "unknown bvh_kind");
+// RT_PT_QUADS=1: the lane kernel walks two-level node records (build_quads).  Exact (the GPU suite
+// passes with it on; test_wavefront_equals_one_kernel_path_tracer runs it), but measured slower,
+// so off by default (tools/ab.py serial frames, profiles/r05/quadab): CFG3-sub 2.133 -> 2.385 ms,
+// CFG5-sub 8.49 -> 9.41, TEAPOT-F depth 10 1.150 -> 1.253, mig29 x16 spp 4 depth 4 3.78 -> 4.40 --
+// a record step costs four slab tests, two box unions and a 128-B load for every lane of the
+// wave whichever branch (leaf, odd half, record) each lane is in, and the lanes' chains shrink less
+// than the step grows.
+#ifndef RT_PT_QUADS_DEFAULT
+#define RT_PT_QUADS_DEFAULT 0
+#endif
+// the environment's part of pack_scene's options
+int pack_options_from_env(PackOptions &o) {
     // RT_BVH (plain / sbvh) picks the tree only where the caller left the default
     if (const char *e = std::getenv("RT_BVH")) {
         if (std::strcmp(e, "sbvh") != 0 && std::strcmp(e, "plain") != 0)
             return fail(RT_ERR_INVALID, std::string("RT_BVH must be 'plain' or 'sbvh', not '") + e + "'");
-        if (bvh_kind == RT_BVH_PLAIN) bvh_kind = std::strcmp(e, "sbvh") == 0 ? RT_BVH_SBVH : RT_BVH_PLAIN;
+        o.bvh_kind = std::strcmp(e, "sbvh") == 0 ? RT_BVH_SBVH : RT_BVH_PLAIN;
     }
-    int rc = ensure_device(d->device);
-    if (rc != RT_OK) return rc;
-
-    rt_scene *s = new rt_scene();
-    s->device = d->device;
-    s->ext = ext;
-    s->num_prims = n;
-    // ---- BVH: prebuilt (validated) or built here
-    if (d->bvh_nodes) {
-        if (!d->bvh_indices || d->bvh_num_nodes < 2) { delete s; return fail(RT_ERR_INVALID, "prebuilt BVH incomplete"); }
-        s->bvh.nodes.resize(d->bvh_num_nodes);
-        std::memcpy(s->bvh.nodes.data(), d->bvh_nodes, sizeof(Node) * d->bvh_num_nodes);
-        s->bvh.indices.assign(d->bvh_indices, d->bvh_indices + n);
-        s->bvh.nodes_used = d->bvh_num_nodes;
-        if ((rc = validate_bvh(s->bvh, n)) != RT_OK) { delete s; return rc; }
-        // depth + widest leaf
-        // depth as Scene::maxDepthBVH (template/scene.h:144-154): interior levels, root leaf = 1
-        std::vector<std::pair<uint32_t, uint32_t>> st{{0, 0}};
-        while (!st.empty()) {
-            auto [k, dd] = st.back();
-            st.pop_back();
-            const Node &nd = s->bvh.nodes[k];
-            if (nd.count > 0) {
-                s->bvh.max_leaf = std::max(s->bvh.max_leaf, nd.count);
-                s->bvh.depth = std::max(s->bvh.depth, k == 0 ? 1u : dd);
-                continue;
-            }
-            st.push_back({nd.leftFirst, dd + 1});
-            st.push_back({nd.leftFirst + 1, dd + 1});
-        }
-    } else if ((rc = (bvh_kind == RT_BVH_SBVH ? build_sbvh : build_bvh)(d->prims, d->transforms, n, s->bvh)) != RT_OK) {
-        delete s;
-        return rc;
-    }
-    if (s->bvh.nodes_used > kMaxNodes) { delete s; return fail(RT_ERR_UNSUPPORTED, "BVH with more than 2^24 nodes (24-bit child index)"); }
-    if (s->bvh.max_leaf > 255) { delete s; return fail(RT_ERR_UNSUPPORTED, "BVH leaf with more than 255 primitives"); }
-    if (s->bvh.depth > 64) { delete s; return fail(RT_ERR_UNSUPPORTED, "BVH deeper than 64 (the reference's stack[64])"); }
-    s->stack_depth = pick_stack(s->bvh.depth);
-    // trees deeper than 60: the lane stacks (depth x 1 KB) leave no room for the walk's words
-    s->walk_fits = (size_t)s->stack_depth * (256u + 4u) * sizeof(uint32_t) <= kLdsLaunchMax;
-
-    // ---- device node array: packed (leftFirst << 8 | count) word in b.z
-    std::vector<float4> nodes(2 * (size_t)s->bvh.nodes_used);
-    for (uint32_t i = 0; i < s->bvh.nodes_used; ++i) {
-        const Node &nd = s->bvh.nodes[i];
-        uint32_t word = (nd.leftFirst << 8) | nd.count;
-        nodes[2 * i] = make_float4(nd.mn[0], nd.mn[1], nd.mn[2], nd.mx[0]);
-        nodes[2 * i + 1] = make_float4(nd.mx[1], nd.mx[2], ubits(word), 0.0f);
-    }
-    std::vector<uint8_t> sticky;
     // the wave walk's cull margin: RT_WALK_MARGIN = its base-2 exponent
-    s->view.walk_margin = 0x1p-12f;
-    if (const char *e = std::getenv("RT_WALK_MARGIN"))
-        s->view.walk_margin = std::ldexp(1.0f, std::max(-40, std::min(-1, std::atoi(e))));
-    mark_sticky(s->bvh, d, nodes, sticky, s->view.walk_margin, s->pinfo, s->sliver_lim);
-    s->pbox.resize(6 * (size_t)n);
-    for (uint32_t id = 0; id < n; ++id) {
-        PrimX x;
-        PrimGeom g;
-        prim_transform(d->prims[id], d->transforms ? d->transforms + 16 * (size_t)id : nullptr, x);
-        prim_geometry(d->prims[id], x, g);
-        const float bx[6] = {g.bmin.x, g.bmin.y, g.bmin.z, g.bmax.x, g.bmax.y, g.bmax.z};
-        for (int c = 0; c < 6; ++c) {
-            s->pbox[6 * (size_t)id + c] = bx[c];
-            if (!std::isfinite(bx[c])) s->boxes_finite = false;
-        }
-        s->pinfo[id] = (uint8_t)(d->prims[id].type | (s->pinfo[id] ? 0x80 : 0));
-    }
-    std::vector<float4> quads;
-    uint32_t quad_root = 0;
-    {
-        bool lanes = RT_PT_QUADS_DEFAULT != 0;
-        if (const char *e = std::getenv("RT_PT_QUADS")) lanes = std::atoi(e) != 0;
-        s->quads = lanes && build_quads(s->bvh, sticky, quads, quad_root);
-        s->quad_lanes = s->quads;
-    }
-    // ---- leaf-order primitive records and per-id shading records; cubes and quads keep
-    // their matrices and data in a side table (8 float4 each)
-    static const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    const uint32_t nrefs = (uint32_t)s->bvh.indices.size();   // leaf slots (an SBVH repeats primitives)
-    std::vector<float4> prims(3 * (size_t)nrefs), shade(2 * (size_t)n), xprims;
-    std::vector<uint32_t> xindex(n, 0);
-    for (uint32_t id = 0; id < n; ++id) {
-        const rt_prim &p = d->prims[id];
-        if (p.type != RT_CUBE && p.type != RT_QUAD) continue;
-        if (p.type == RT_CUBE) s->has_cubes = true;
-        PrimX x;
-        prim_transform(p, d->transforms ? d->transforms + 16 * (size_t)id : nullptr, x);
-        xindex[id] = (uint32_t)(xprims.size() / 8);
-        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.Minv[4 * r], x.Minv[4 * r + 1], x.Minv[4 * r + 2], x.Minv[4 * r + 3]));
-        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.M[4 * r], x.M[4 * r + 1], x.M[4 * r + 2], x.M[4 * r + 3]));
-        if (p.type == RT_CUBE) {   // data[0] = -0.5 size, data[1] = 0.5 size (Primitive.h:724-725)
-            const f3 sz = mk(p.v[3], p.v[4], p.v[5]), a = -0.5f * sz, b = 0.5f * sz;
-            xprims.push_back(make_float4(a.x, a.y, a.z, 0.0f));
-            xprims.push_back(make_float4(b.x, b.y, b.z, 0.0f));
-        } else {                   // data[0].x = 0.5 size (Primitive.h:737)
-            xprims.push_back(make_float4(0.5f * p.v[0], 0.0f, 0.0f, 0.0f));
-            xprims.push_back(make_float4(0, 0, 0, 0));
-        }
-    }
-    for (uint32_t id = 0; id < n; ++id) {
-        const rt_prim &p = d->prims[id];
-        float4 s0, s1 = make_float4(ubits((uint32_t)p.type), 0, 0, 0);
-        if (p.type == RT_CUBE || p.type == RT_QUAD) {
-            const float4 *x = &xprims[8 * (size_t)xindex[id]];
-            // quad: constant normal TransformVector((0,-1,0), Transform) (Primitive.h:306-307)
-            f3 N = p.type == RT_QUAD ? tvec_host(x[3], x[4], x[5], mk(0, -1, 0)) : mk(0, 0, 0);
-            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
-            s1.z = ubits(xindex[id]);
-        } else if (p.type == RT_TRIANGLE) {
-            f3 d0 = mk(p.v[0], p.v[1], p.v[2]), d1 = mk(p.v[3], p.v[4], p.v[5]), d2 = mk(p.v[6], p.v[7], p.v[8]);
-            f3 N = tvec(I16, normalize(cross(d2 - d0, d1 - d0)));      // Primitive.h:308-310
-            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
-        } else if (p.type == RT_SPHERE) {
-            float T[16];
-            translate_matrix(p.v[0], p.v[1], p.v[2], T);
-            f3 c = tpos(T, mk(0, 0, 0));
-            s0 = make_float4(c.x, c.y, c.z, ibits(p.material));
-            s1.y = 1.0f / p.v[3];                                      // data[0].z
-        } else {
-            s0 = make_float4(p.v[0], p.v[1], p.v[2], ibits(p.material));
-        }
-        shade[2 * id] = s0;
-        shade[2 * id + 1] = s1;
-    }
-    for (uint32_t k = 0; k < nrefs; ++k) {
-        const uint32_t id = s->bvh.indices[k];
-        const rt_prim &p = d->prims[id];
-        float4 *q = &prims[3 * (size_t)k];
-        if (p.type == RT_TRIANGLE) {
-            f3 A = tpos(I16, mk(p.v[0], p.v[1], p.v[2]));                 // Intersect, Primitive.h:249-254
-            f3 B = tpos(I16, mk(p.v[3], p.v[4], p.v[5]));
-            f3 C = tpos(I16, mk(p.v[6], p.v[7], p.v[8]));
-            f3 AB = B - A, AC = C - A;
-            q[0] = make_float4(A.x, A.y, A.z, ibits((int)id));
-            q[1] = make_float4(AB.x, AB.y, AB.z, ubits(T_TRI));
-            q[2] = make_float4(AC.x, AC.y, AC.z, 0.0f);
-        } else if (p.type == RT_SPHERE) {
-            float T[16];
-            translate_matrix(p.v[0], p.v[1], p.v[2], T);
-            f3 c = tpos(T, mk(0, 0, 0));
-            float r = p.v[3];
-            q[0] = make_float4(c.x, c.y, c.z, ibits((int)id));
-            q[1] = make_float4(r * r, 0.0f, 0.0f, ubits(T_SPH)); // data[0].y
-            q[2] = make_float4(0, 0, 0, 0);
-        } else if (p.type == RT_PLANE) {
-            q[0] = make_float4(p.v[0], p.v[1], p.v[2], ibits((int)id));
-            q[1] = make_float4(p.v[3], 0.0f, 0.0f, ubits(T_PLANE));
-            q[2] = make_float4(0, 0, 0, 0);
-        } else {
-            q[0] = make_float4(0, 0, 0, ibits((int)id));
-            q[1] = make_float4(ubits(xindex[id]), 0.0f, 0.0f, ubits(p.type == RT_CUBE ? T_CUBE : T_QUAD));
-            q[2] = make_float4(0, 0, 0, 0);
-        }
-    }
-    // ---- textures, concatenated
-    std::vector<uint32_t> texels, tex_offsets;
-    for (uint32_t i = 0; i < d->num_textures; ++i) {
-        const rt_texture &t = d->textures[i];
-        tex_offsets.push_back((uint32_t)texels.size());
-        texels.insert(texels.end(), t.pixels, t.pixels + (size_t)t.width * t.height);
-    }
-    if (texels.empty()) texels.push_back(0);
-    if (xprims.empty()) xprims.push_back(make_float4(0, 0, 0, 0));
-    // ---- materials
-    std::vector<DevMaterial> mats(d->num_materials);
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const rt_material &m = d->materials[i];
-        DevMaterial &o = mats[i];
-        std::memset(&o, 0, sizeof(o));
-        o.kind = m.kind;
-        for (int c = 0; c < 3; ++c) { o.c0[c] = m.color[c]; o.c1[c] = m.color2[c]; }
-        o.ior = m.ior;
-        // Checkerboard.h:6-14, TextureMaterial.h:6-17 (short ctor: diffuse 1, specular 0),
-        // DSMix.h:6-9 (always clamped): clamp = fmaxf(a, fminf(f, b)), precomp.h:782
-        if (m.kind == RT_CHECKERBOARD || m.kind == RT_TEXTURE || m.kind == RT_DSMIX) {
-            if (m.diffuse < 0.0f && m.kind != RT_DSMIX) { o.diffuse = 1.0f; o.specular = 0.0f; }
-            else { o.diffuse = tmax(0.0f, tmin(m.diffuse, 1.0f)); o.specular = 1.0f - o.diffuse; }
-        }
-        if (m.kind == RT_TEXTURE) {
-            const rt_texture &t = d->textures[m.texture];
-            o.tex_off = tex_offsets[m.texture];
-            o.tex_w = t.width; o.tex_h = t.height;
-        }
-        o.flag = material_flag(m, o.diffuse, o.specular);
-    }
-    // ---- sky
-    std::vector<uint32_t> sky;
-    uint32_t sw = 1024, sh = 512;
-    if (d->sky_pixels) {
-        sw = d->sky_width; sh = d->sky_height;
-        sky.assign(d->sky_pixels, d->sky_pixels + (size_t)sw * sh);
-    } else {
-        sky.assign((size_t)sw * sh, 0x406080u);
-    }
-    bool sky_const = std::all_of(sky.begin(), sky.end(), [&](uint32_t v) { return v == sky[0]; });
+    if (const char *e = std::getenv("RT_WALK_MARGIN")) o.walk_margin = std::ldexp(1.0f, std::max(-40, std::min(-1, std::atoi(e))));
+    // a sliver's sine limit 2^RT_WALK_STICKY (>= 0: no triangle is one); RT_WALK_STICKY_SPHERES=0: A/B only
+    if (const char *e = std::getenv("RT_WALK_STICKY")) o.sliver_lim = std::atoi(e) >= 0 ? 0.0 : std::ldexp(1.0, std::atoi(e));
+    if (const char *e = std::getenv("RT_WALK_STICKY_SPHERES")) o.sticky_spheres = std::atoi(e) != 0;
+    o.quads = RT_PT_QUADS_DEFAULT != 0;
+    if (const char *e = std::getenv("RT_PT_QUADS")) o.quads = std::atoi(e) != 0;
+    return RT_OK;
+}
 
-    rc = RT_OK;
-    if (rc == RT_OK) rc = upload(&s->d_nodes, nodes);
-    if (rc == RT_OK) rc = upload(&s->d_prims, prims);
-    if (rc == RT_OK) rc = upload(&s->d_shade, shade);
-    if (rc == RT_OK) rc = upload(&s->d_mats, mats);
-    if (rc == RT_OK) rc = upload(&s->d_sky, sky);
-    if (rc == RT_OK) rc = upload(&s->d_xprims, xprims);
-    if (rc == RT_OK) rc = upload(&s->d_tex, texels);
-    if (rc == RT_OK && s->quads) rc = upload(&s->d_quads, quads);
-    if (rc == RT_OK && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = fail(RT_ERR_HIP, "hipStreamCreate failed");
-    if (rc != RT_OK) { free_scene(s); return rc; }
-
-    SceneView &v = s->view;
-    v.nodes = (const float4 *)s->d_nodes;
-    v.prims = (const float4 *)s->d_prims;
-    v.shade = (const float4 *)s->d_shade;
-    v.mats = (const DevMaterial *)s->d_mats;
-    v.sky = (const uint32_t *)s->d_sky;
-    v.xprims = (const float4 *)s->d_xprims;
-    v.tex = (const uint32_t *)s->d_tex;
-    v.quads = s->quads ? (const float4 *)s->d_quads : nullptr;
-    v.quad_root = quad_root;
-    v.quad_lanes = 0;
-    v.sky_w = sw; v.sky_h = sh;
-    v.sky_const = sky_const ? 1 : 0;
-    {
-        uint32_t p = sky[0];
-        f3 c = mk((float)((p >> 16) & 255), (float)((p >> 8) & 255), (float)(p & 255)) * kSKY;
-        v.sky_rgb[0] = c.x; v.sky_rgb[1] = c.y; v.sky_rgb[2] = c.z;
-    }
-    const rt_prim &L = d->prims[0];
-    PrimX LX;
-    prim_transform(L, d->transforms ? d->transforms : nullptr, LX);
-    std::memcpy(v.light_M, LX.M, sizeof(v.light_M));
-    f3 lc = tpos(LX.M, mk(0, 0, 0));
-    v.light_c[0] = lc.x; v.light_c[1] = lc.y; v.light_c[2] = lc.z;
-    v.light_mat = L.material;
-    v.light_quad = L.type == RT_QUAD;
-    if (v.light_quad) {
-        v.light_qsize = 0.5f * L.v[0];
-        const float side = 2.0f * v.light_qsize;                      // GetArea, Primitive.h:461-463
-        v.light_area = side * side;
-        const f3 N = tvec(LX.M, mk(0, -1, 0));
-        v.light_N[0] = N.x; v.light_N[1] = N.y; v.light_N[2] = N.z;
-    } else {
-        v.light_r = L.v[3];
-        v.light_r2 = L.v[3] * L.v[3];
-        v.light_invr = 1.0f / L.v[3];
-        v.light_area = 4.0f * kPI * v.light_r2;                        // Primitive.h:452
-    }
-    const Node &root = s->bvh.nodes[0];
-    v.root_word = (root.leftFirst << 8) | root.count;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0)
-            s->num_cus = (uint32_t)prop.multiProcessorCount;
-    }
-    v.stack_entries = s->stack_depth;
+// the scene's launch policy: defaults from the tree, overridden by the environment (A/B runs)
+void scene_knobs_from_env(rt_scene *s) {
     // Primary+shadow frames read the nodes from global memory (L1/L2-resident, 256-thread
     // workgroups).  The LDS-node kernels of rounds 1-3 (48-B pairs + u16 stacks in two 512-thread
     // workgroups per CU, or 64-B pairs in one 1024-thread group) lost by 12 % once the ray
@@ -804,7 +334,7 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     // XCD-grouped tile order for scenes whose nodes + primitive slots exceed one XCD's 4 MB L2:
     // mig29 x16 (11.6 MB) 0.449 -> 0.406 ms; a cache-resident TEAPOT-F loses with it (4K
     // 0.377 -> 0.441 ms, 720p neutral) -- profiles/r02/ab_xcd_*.json.  RT_XCD_ORDER=0/1 forces it.
-    s->xcd_order = (size_t)s->bvh.nodes_used * 32u + (size_t)n * 48u > (4u << 20);
+    s->xcd_order = (size_t)s->bvh.nodes_used * 32u + (size_t)s->num_prims * 48u > (4u << 20);
     if (const char *e = std::getenv("RT_XCD_ORDER")) s->xcd_order = std::atoi(e) != 0;
     if (const char *e = std::getenv("RT_PT_PIPELINE")) s->pt_pipeline = std::atoi(e) != 0;
     if (const char *e = std::getenv("RT_PT_SLOTS")) s->pt_slots = (uint32_t)std::max(2, std::min((int)kPtMaxSlots, std::atoi(e)));
@@ -814,30 +344,65 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     if (const char *e = std::getenv("RT_TUNE_DELAY_MS")) s->tune_delay_ms = (float)std::max(0.0, std::atof(e));
     if (const char *e = std::getenv("RT_PT_MEM_MB"))
         s->pt_mem_bytes = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) << 20;
-    // every child box inside its parent's, compared as floats (the wave walk's pops and its leaf
-    // check rely on it: a child's slab entry is then never below its parent's)
-    for (uint32_t i = 0; i < s->bvh.nodes_used && s->nested; ++i) {
-        if (i == 1) continue;
-        const Node &nd = s->bvh.nodes[i];
-        if (nd.count > 0) continue;
-        for (uint32_t c = nd.leftFirst; c < nd.leftFirst + 2 && s->nested; ++c) {
-            const Node &ch = s->bvh.nodes[c];
-            for (int a = 0; a < 3; ++a)
-                if (!(ch.mn[a] >= nd.mn[a]) || !(ch.mx[a] <= nd.mx[a])) s->nested = false;
-        }
-    }
     // camera-ray walk: wave-coherent vs per-lane (RT_WAVE_PRIMARY=0/1 overrides the policy)
-    v.wave_primary = 0;
     const bool wave_ok = !s->has_cubes && s->nested && s->walk_fits;
     s->walk = wave_ok ? RT_WALK_AUTO : RT_WALK_LANE;
     if (const char *e = std::getenv("RT_WAVE_PRIMARY")) s->walk = std::atoi(e) != 0 && wave_ok ? RT_WALK_WAVE : RT_WALK_LANE;
-    v.bounds_finite = 1;
-    for (uint32_t i = 0; i < s->bvh.nodes_used && v.bounds_finite; ++i) {
-        if (i == 1) continue;
-        const Node &nd = s->bvh.nodes[i];
-        for (int c = 0; c < 3; ++c)
-            if (!std::isfinite(nd.mn[c]) || !std::isfinite(nd.mx[c])) v.bounds_finite = 0;
+}
+
+int scene_create(const rt_scene_desc *d, rt_scene **out) {
+    if (!d || !out) return fail(RT_ERR_INVALID, "rt_scene_create: empty or null description");
+    *out = nullptr;
+    PackOptions o;
+    int rc = pack_options_from_env(o);
+    if (rc != RT_OK) return rc;
+    // the description's errors come before the device's: a machine without a GPU reports them too
+    ScenePack p;
+    if ((rc = pack_scene(d, o, p)) != RT_OK) return rc;
+    if ((rc = ensure_device(d->device)) != RT_OK) return rc;
+
+    rt_scene *s = new rt_scene();
+    s->device = d->device;
+    s->num_prims = d->num_prims;
+    s->stack_depth = p.stack_depth;
+    s->ext = p.ext;
+    s->has_cubes = p.has_cubes;
+    s->nested = p.nested;
+    s->walk_fits = p.walk_fits;
+    s->boxes_finite = p.boxes_finite;
+    s->quads = s->quad_lanes = p.has_quads;
+    s->sliver_lim = o.sliver_lim;
+    rc = upload(&s->d_nodes, p.nodes);
+    if (rc == RT_OK) rc = upload(&s->d_prims, p.prims);
+    if (rc == RT_OK) rc = upload(&s->d_shade, p.shade);
+    if (rc == RT_OK) rc = upload(&s->d_mats, p.mats);
+    if (rc == RT_OK) rc = upload(&s->d_sky, p.sky);
+    if (rc == RT_OK) rc = upload(&s->d_xprims, p.xprims);
+    if (rc == RT_OK) rc = upload(&s->d_tex, p.texels);
+    if (rc == RT_OK && s->quads) rc = upload(&s->d_quads, p.quads);
+    if (rc == RT_OK && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
+        rc = fail(RT_ERR_HIP, "hipStreamCreate failed");
+    if (rc != RT_OK) { free_scene(s); return rc; }
+    s->bvh = std::move(p.bvh);
+    s->pinfo = std::move(p.pinfo);
+    s->pbox = std::move(p.pbox);
+
+    SceneView &v = s->view;
+    v = p.view;
+    v.nodes = (const float4 *)s->d_nodes;
+    v.prims = (const float4 *)s->d_prims;
+    v.shade = (const float4 *)s->d_shade;
+    v.mats = (const DevMaterial *)s->d_mats;
+    v.sky = (const uint32_t *)s->d_sky;
+    v.xprims = (const float4 *)s->d_xprims;
+    v.tex = (const uint32_t *)s->d_tex;
+    v.quads = s->quads ? (const float4 *)s->d_quads : nullptr;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0)
+            s->num_cus = (uint32_t)prop.multiProcessorCount;
     }
+    scene_knobs_from_env(s);
     *out = s;
     return RT_OK;
 }
@@ -1922,9 +1487,10 @@ int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
         HIP_TRY(hipMemcpy(dn.data(), s->d_nodes, sizeof(float4) * dn.size(), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < s->bvh.nodes_used; ++i) {
             Node &nd = s->bvh.nodes[i];
-            const float4 a = dn[2 * (size_t)i], b = dn[2 * (size_t)i + 1];
-            nd.mn[0] = a.x; nd.mn[1] = a.y; nd.mn[2] = a.z;
-            nd.mx[0] = a.w; nd.mx[1] = b.x; nd.mx[2] = b.y;
+            f3 mn, mx;
+            node_box(dn[2 * (size_t)i], dn[2 * (size_t)i + 1], mn, mx);
+            nd.mn[0] = mn.x; nd.mn[1] = mn.y; nd.mn[2] = mn.z;
+            nd.mx[0] = mx.x; nd.mx[1] = mx.y; nd.mx[2] = mx.z;
         }
         s->bvh_stale = false;
     }
@@ -1942,8 +1508,7 @@ static int ensure_refit(rt_scene *s) {
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t id = s->bvh.indices[k];
         const float *b = &s->pbox[6 * (size_t)id];
-        box[2 * (size_t)k] = make_float4(b[0], b[1], b[2], ubits((s->pinfo[id] & 0x80) ? 1u : 0u));
-        box[2 * (size_t)k + 1] = make_float4(b[3], b[4], b[5], 0.0f);
+        slot_box(mk(b[0], b[1], b[2]), mk(b[3], b[4], b[5]), (s->pinfo[id] & 0x80) != 0, &box[2 * (size_t)k]);
     }
     int rc = upload(&s->d_slot_of, s->plan.slot_of);
     if (rc == RT_OK) rc = upload(&s->d_slot_box, box);

@@ -25,6 +25,7 @@
 #include <zlib.h>
 
 #include "rt_internal.h"
+#include "rt_records.h"
 
 namespace rt {
 
@@ -313,10 +314,8 @@ void prim_geometry(const rt_prim &p, const PrimX &x, PrimGeom &g) {
         g.bmax = mk(1e30f, 1e30f, 1e30f);
     } else {
         f3 d0 = mk(p.v[0], p.v[1], p.v[2]), d1 = mk(p.v[3], p.v[4], p.v[5]), d2 = mk(p.v[6], p.v[7], p.v[8]);
-        f3 A = tpos(kIdentity, d0), B = tpos(kIdentity, d1), C = tpos(kIdentity, d2);
         g.centroid = tpos(kIdentity, ((d0 + d1) + d2) / 3.0f);
-        g.bmin = fmin3(A, fmin3(B, C));
-        g.bmax = fmax3(A, fmax3(B, C));
+        tri_box(p.v, g.bmin, g.bmax);
     }
 }
 
@@ -522,6 +521,35 @@ class Builder {
     }
 };
 }  // namespace
+
+int walk_tree(const Node *N, uint32_t nodes_used, size_t slots, TreeWalk &w) {
+    w.parent.assign(nodes_used, ~0u);
+    w.depth.assign(nodes_used, 0);
+    w.order.resize(nodes_used);
+    w.max_leaf = 0;
+    uint32_t met = 0;
+    std::vector<uint32_t> st{0u};
+    while (!st.empty()) {
+        const uint32_t k = st.back();
+        st.pop_back();
+        if (met >= nodes_used) return kTreeCycle;   // node 1 is never a child: a tree meets fewer
+        w.order[met++] = k;
+        const Node &nd = N[k];
+        if (nd.count > 0) {
+            if ((uint64_t)nd.leftFirst + nd.count > slots) return kTreeLeafRange;
+            w.max_leaf = std::max(w.max_leaf, nd.count);
+            continue;
+        }
+        const uint32_t l = nd.leftFirst;
+        if (l < 2 || (uint64_t)l + 1 >= nodes_used) return kTreeChildRange;
+        w.parent[l] = w.parent[l + 1] = k;
+        w.depth[l] = w.depth[l + 1] = w.depth[k] + 1;
+        st.push_back(l + 1);
+        st.push_back(l);
+    }
+    w.order.resize(met);
+    return kTreeOk;
+}
 
 int build_bvh(const rt_prim *prims, const float *transforms, uint32_t n, Bvh &out) {
     if (n == 0) return fail(RT_ERR_INVALID, "scene has no primitives");
@@ -962,30 +990,21 @@ int rt_bvh_refit_host(const rt_prim *prims, const float *transforms, uint32_t n,
             if (seen[indices[k]]) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: a primitive sits in two leaves (an SBVH); plain trees only");
             seen[indices[k]] = 1;
         }
-        std::vector<uint32_t> order, st{0u};
-        std::vector<uint8_t> slot(n, 0);
-        while (!st.empty()) {   // pre-order; children in range, every leaf slot met once
-            const uint32_t k = st.back();
-            st.pop_back();
-            if (order.size() >= nodes_used) return fail(RT_ERR_INVALID, "rt_bvh_refit_host: the tree has a cycle");
-            order.push_back(k);
-            const Node &nd = N[k];
-            if (nd.count > 0) {
-                if ((uint64_t)nd.leftFirst + nd.count > n)
-                    return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: a leaf reaches past the n indices (an SBVH); plain trees only");
-                for (uint32_t s = nd.leftFirst; s < nd.leftFirst + nd.count; ++s) {
-                    if (slot[s]) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: leaves overlap; plain trees only");
-                    slot[s] = 1;
-                }
-                continue;
-            }
-            if (nd.leftFirst < 2 || (uint64_t)nd.leftFirst + 1 >= nodes_used)
-                return fail(RT_ERR_INVALID, "rt_bvh_refit_host: child pair out of range");
-            st.push_back(nd.leftFirst + 1);
-            st.push_back(nd.leftFirst);
+        TreeWalk w;
+        switch (walk_tree(N.data(), nodes_used, n, w)) {
+        case kTreeCycle: return fail(RT_ERR_INVALID, "rt_bvh_refit_host: the tree has a cycle");
+        case kTreeLeafRange:
+            return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: a leaf reaches past the n indices (an SBVH); plain trees only");
+        case kTreeChildRange: return fail(RT_ERR_INVALID, "rt_bvh_refit_host: child pair out of range");
         }
-        for (size_t i = order.size(); i-- > 0;) {
-            Node &nd = N[order[i]];
+        std::vector<uint8_t> slot(n, 0);   // every leaf slot met once
+        for (uint32_t k : w.order)
+            for (uint32_t s = N[k].leftFirst; N[k].count > 0 && s < N[k].leftFirst + N[k].count; ++s) {
+                if (slot[s]) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_host: leaves overlap; plain trees only");
+                slot[s] = 1;
+            }
+        for (size_t i = w.order.size(); i-- > 0;) {
+            Node &nd = N[w.order[i]];
             f3 mn, mx;
             if (nd.count > 0) {
                 mn = mk(1e30f, 1e30f, 1e30f);

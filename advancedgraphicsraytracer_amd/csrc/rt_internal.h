@@ -1,9 +1,10 @@
-// rt_internal.h -- host-side internals shared by rt_host.cpp and rt_device.hip.
+// rt_internal.h -- host-side internals shared by rt_host.cpp, rt_scene_pack.cpp and rt_device.hip.
 #pragma once
 #include <string>
 #include <vector>
 
 #include "../../include/rt_amd.h"
+#include "rt_dev_types.h"
 #include "rt_math.h"
 
 namespace rt {
@@ -42,6 +43,41 @@ struct Bvh {
 int build_bvh(const rt_prim *prims, const float *transforms, uint32_t n, Bvh &out);
 // Spatial-split BVH (rt_sbvh.cpp): indices hold references (a primitive may repeat)
 int build_sbvh(const rt_prim *prims, const float *transforms, uint32_t n, Bvh &out);
+
+// The one walk of a node array (rt_host.cpp): pre-order from the root, left child first, over the
+// first nodes_used nodes with leaves inside `slots` leaf slots.  order = the nodes as met, and per
+// node index its parent (~0u: the root, or a node the walk never met) and its depth (root 0).
+struct TreeWalk {
+    std::vector<uint32_t> order, parent, depth;
+    uint32_t max_leaf = 0;   // the widest leaf's count
+};
+enum { kTreeOk = 0, kTreeChildRange, kTreeLeafRange, kTreeCycle };
+// kTreeChildRange: a child pair outside [2, nodes_used); kTreeLeafRange: a leaf past the slots;
+// kTreeCycle: more nodes met than a tree of nodes_used nodes has.  The caller words the error.
+int walk_tree(const Node *N, uint32_t nodes_used, size_t slots, TreeWalk &out);
+
+// Scene creation up to the upload (rt_scene_pack.cpp): no HIP call, no environment variable.
+struct PackOptions {
+    int bvh_kind = RT_BVH_PLAIN;      // the tree built where the description brings none
+    float walk_margin = 0x1p-12f;     // the wave walk's cull margin
+    double sliver_lim = 0x1p-8;       // tri_sliver's sine limit (0: no triangle is a sliver)
+    bool sticky_spheres = true;       // spheres and quads make their nodes sticky
+    bool quads = false;               // build the two-level node records (build_quads)
+};
+struct ScenePack {            // everything scene_create computes before it touches the device
+    Bvh bvh;
+    std::vector<float4> nodes, prims, shade, xprims, quads;
+    std::vector<DevMaterial> mats;
+    std::vector<uint32_t> sky, texels;
+    SceneView view;           // scalar fields only; pointers stay null
+    // per primitive its type | sticky << 7 and its box (prim_geometry; 6 floats): what a refit
+    // needs of the primitives that do not move
+    std::vector<uint8_t> pinfo;
+    std::vector<float> pbox;
+    uint32_t stack_depth;     // LDS stack entries per lane
+    bool ext, has_cubes, nested, walk_fits, boxes_finite, has_quads;
+};
+int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &out);
 
 // frame size and device of a renderer (rt_multi.cpp)
 int renderer_geometry(const rt_renderer *r, uint32_t *W, uint32_t *H, int *device);

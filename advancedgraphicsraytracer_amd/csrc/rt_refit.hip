@@ -3,9 +3,9 @@
 // The tree's topology, primitive ids and leaf membership stay; three kernels rewrite what moves:
 //   k_update_tris      one lane per updated triangle: its leaf-slot record (A | id, B-A | T_TRI, C-A),
 //                      the normal of its shading record, its box (min / max of the three vertices,
-//                      Primitive.h:319-388) and its sliver flag (mark_sticky's test) -- the same
-//                      rt_math.h expressions as scene_create under the same -ffp-contract=off, so
-//                      the records equal those of a fresh rt_scene_create on the new vertices;
+//                      Primitive.h:319-388) and its sliver flag -- the rt_records.h encoders that
+//                      scene creation runs, under the same -ffp-contract=off, so the records
+//                      equal those of a fresh rt_scene_create on the new vertices;
 //   k_refit_treelets   one workgroup per treelet (a whole subtree of at most kTreeletNodes nodes):
 //                      leaves fold their slots' boxes as Scene::UpdateNodeBounds does
 //                      (template/scene.h:855-865), then one height at a time, a barrier between
@@ -21,7 +21,7 @@
 
 #include <algorithm>
 
-#include "rt_dev_types.h"
+#include "rt_records.h"
 
 namespace rt {
 
@@ -37,16 +37,10 @@ bool build_refit_plan(const Bvh &b, uint32_t num_prims, RefitPlan &out) {
         out.slot_of[id] = k;
     }
     // pre-order from the root; sizes and heights in reverse
-    std::vector<uint32_t> order, parent(used, ~0u), size(used, 0), height(used, 0);
-    order.reserve(used);
-    std::vector<uint32_t> st{0u};
-    while (!st.empty()) {
-        const uint32_t k = st.back();
-        st.pop_back();
-        order.push_back(k);
-        if (N[k].count > 0) continue;
-        for (uint32_t c : {N[k].leftFirst + 1, N[k].leftFirst}) { parent[c] = k; st.push_back(c); }
-    }
+    TreeWalk w;
+    if (walk_tree(N, used, num_prims, w) != kTreeOk) return false;
+    const std::vector<uint32_t> &order = w.order;
+    std::vector<uint32_t> size(used, 0), height(used, 0);
     for (size_t i = order.size(); i-- > 0;) {
         const uint32_t k = order[i];
         size[k] = 1;
@@ -66,17 +60,11 @@ bool build_refit_plan(const Bvh &b, uint32_t num_prims, RefitPlan &out) {
         out.lvl.push_back((uint32_t)out.list.size());
     };
     std::vector<uint32_t> top, sub;
-    for (uint32_t k : order) {   // pre-order: a treelet's nodes follow its root
+    for (size_t i = 0; i < order.size(); ++i) {   // pre-order: a treelet's size[k] nodes start at its root
+        const uint32_t k = order[i];
         if (size[k] > kTreeletNodes) { top.push_back(k); continue; }
-        if (k != 0 && size[parent[k]] <= kTreeletNodes) continue;   // inside a treelet
-        sub.clear();
-        st.assign(1, k);
-        while (!st.empty()) {
-            const uint32_t j = st.back();
-            st.pop_back();
-            sub.push_back(j);
-            if (N[j].count == 0) { st.push_back(N[j].leftFirst + 1); st.push_back(N[j].leftFirst); }
-        }
+        if (k != 0 && size[w.parent[k]] <= kTreeletNodes) continue;   // inside a treelet
+        sub.assign(order.begin() + i, order.begin() + i + size[k]);
         emit(sub);
         ++out.ntreelets;
     }
@@ -101,42 +89,16 @@ __global__ void __launch_bounds__(256) k_update_tris(RefitArgs A, uint32_t first
     if (i >= count) return;
     const uint32_t id = first + i, slot = A.slot_of[id];
     const float *p = verts + 9u * (size_t)i;
-    const float I16[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    const f3 d0 = mk(p[0], p[1], p[2]), d1 = mk(p[3], p[4], p[5]), d2 = mk(p[6], p[7], p[8]);
-    const f3 N = tvec(I16, normalize(cross(d2 - d0, d1 - d0)));      // Primitive.h:308-310
-    const f3 a = tpos(I16, d0), b = tpos(I16, d1), c = tpos(I16, d2);  // Intersect, Primitive.h:249-254
-    const f3 AB = b - a, AC = c - a;
+    const f3 N = tri_normal(p);
     A.shade[2 * (size_t)id] = make_float4(N.x, N.y, N.z, A.shade[2 * (size_t)id].w);
-    float4 *q = A.prims + 3 * (size_t)slot;
-    q[0] = make_float4(a.x, a.y, a.z, __int_as_float((int)id));
-    q[1] = make_float4(AB.x, AB.y, AB.z, __uint_as_float(T_TRI));
-    q[2] = make_float4(AC.x, AC.y, AC.z, 0.0f);
-    // mark_sticky's sliver test, in double on the float vertices
-    double v[3][3], e[3][3], len[3];
-    for (int k = 0; k < 3; ++k)
-        for (int x = 0; x < 3; ++x) v[k][x] = p[3 * k + x];
-    for (int k = 0; k < 3; ++k) {
-        for (int x = 0; x < 3; ++x) e[k][x] = v[(k + 1) % 3][x] - v[k][x];
-        len[k] = sqrt(e[k][0] * e[k][0] + e[k][1] * e[k][1] + e[k][2] * e[k][2]);
-    }
-    const double cx = e[0][1] * e[2][2] - e[0][2] * e[2][1], cy = e[0][2] * e[2][0] - e[0][0] * e[2][2],
-                 cz = e[0][0] * e[2][1] - e[0][1] * e[2][0];
-    const double area2 = sqrt(cx * cx + cy * cy + cz * cz);
-    // the two longest edges in ascending order: drop the shortest (ties: any, the values are the same)
-    double l1, l2;
-    if (len[0] <= len[1] && len[0] <= len[2]) { l1 = len[1]; l2 = len[2]; }
-    else if (len[1] <= len[0] && len[1] <= len[2]) { l1 = len[0]; l2 = len[2]; }
-    else { l1 = len[0]; l2 = len[1]; }
-    if (l1 > l2) { const double t = l1; l1 = l2; l2 = t; }
-    const bool sliver = !(area2 >= A.sliver_lim * l1 * l2);
-    const f3 mn = fmin3(a, fmin3(b, c)), mx = fmax3(a, fmax3(b, c));   // Primitive.h:319-388
-    A.slot_box[2 * (size_t)slot] = make_float4(mn.x, mn.y, mn.z, __uint_as_float(sliver ? 1u : 0u));
-    A.slot_box[2 * (size_t)slot + 1] = make_float4(mx.x, mx.y, mx.z, 0.0f);
+    tri_record(p, id, A.prims + 3 * (size_t)slot);
+    f3 mn, mx;
+    tri_box(p, mn, mx);
+    slot_box(mn, mx, tri_sliver(p, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
 }
 
 __device__ __forceinline__ void refit_node(const RefitArgs &A, uint32_t k) {
-    const float4 old = A.nodes[2 * (size_t)k + 1];
-    const uint32_t word = __float_as_uint(old.z), cnt = word & 255u, lf = word >> 8;
+    const uint32_t word = fbits(A.nodes[2 * (size_t)k + 1].z), cnt = word & 255u, lf = word >> 8;
     f3 mn, mx;
     bool sticky = false;
     if (cnt) {   // UpdateNodeBounds over the leaf's slots
@@ -146,17 +108,19 @@ __device__ __forceinline__ void refit_node(const RefitArgs &A, uint32_t k) {
             const float4 lo = A.slot_box[2 * (size_t)s], hi = A.slot_box[2 * (size_t)s + 1];
             mn = fmin3(mn, mk(lo.x, lo.y, lo.z));
             mx = fmax3(mx, mk(hi.x, hi.y, hi.z));
-            sticky = sticky || __float_as_uint(lo.w) != 0u;
+            sticky = sticky || slot_sticky(lo);
         }
     } else {
         const float4 *c = A.nodes + 2 * (size_t)lf;
         const float4 l0 = c[0], l1 = c[1], r0 = c[2], r1 = c[3];
-        mn = fmin3(mk(l0.x, l0.y, l0.z), mk(r0.x, r0.y, r0.z));
-        mx = fmax3(mk(l0.w, l1.x, l1.y), mk(r0.w, r1.x, r1.y));
-        sticky = l1.w == HUGE_VALF || r1.w == HUGE_VALF;
+        f3 lmn, lmx, rmn, rmx;
+        node_box(l0, l1, lmn, lmx);
+        node_box(r0, r1, rmn, rmx);
+        mn = fmin3(lmn, rmn);
+        mx = fmax3(lmx, rmx);
+        sticky = is_sticky(l1.w) || is_sticky(r1.w);
     }
-    A.nodes[2 * (size_t)k] = make_float4(mn.x, mn.y, mn.z, mx.x);
-    A.nodes[2 * (size_t)k + 1] = make_float4(mx.y, mx.z, old.z, sticky ? HUGE_VALF : A.margin);
+    node_pack(mn, mx, word, walk_word(sticky, A.margin), A.nodes + 2 * (size_t)k);
 }
 
 // group g's heights in turn; every wave of the workgroup takes every barrier

@@ -1,0 +1,469 @@
+// rt_scene_pack.cpp -- scene creation up to the upload: a description in, every device record out
+// (ScenePack, rt_internal.h).  No HIP call and no environment variable, so the bit-critical packing
+// runs and is checked without a device (tests/cpp/scene_pack_host.cpp); rt_device.hip uploads the
+// result.  The record layouts are in rt_device.hip's header comment, their encoders in rt_records.h.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rt_internal.h"
+#include "rt_records.h"
+
+namespace rt {
+namespace {
+
+// LDS stack entries per lane: a traversal pushes at most one entry per tree level, so the tree
+// depth is enough.  Rounding it up to 8 cost occupancy where the stacks bound the workgroups
+// per CU (mig29 x16: 26 levels, 32 KB per workgroup -> 5 per CU; exact: 26 KB -> 6): CFG3-sub
+// 1.79 -> 1.65 ms, CFG5-sub 7.58 -> 7.47 ms, mig29 x16 0.330 -> 0.321 ms, TEAPOT-F unchanged
+// (round 3, profiles/r03/ab_stack/).
+#ifndef RT_STACK_ROUND
+#define RT_STACK_ROUND 1u
+#endif
+uint32_t pick_stack(uint32_t depth) {   // entries needed <= tree depth (rounded up to RT_STACK_ROUND)
+    uint32_t need = depth < 2 ? 2 : depth;
+    return (need + RT_STACK_ROUND - 1u) / RT_STACK_ROUND * RT_STACK_ROUND;
+}
+
+// Two-level node records (the path tracer's lane kernel, k_pt_lanes<.., true>): one 128-B
+// record per interior node x at even depth (the root at 0) holding the node entries of x's
+// grandchildren -- slots 2h, 2h+1 = the children of x's child h -- or, for a leaf child h, that
+// leaf's own entry in slot 2h (flag bit 0 in its .w word).  One load then serves two binary
+// levels: the walk tests x's children on boxes rebuilt as the union of their children's (the
+// reference's node bounds ARE that union -- each node's box is the min / max over its primitives'
+// bounds, Scene::UpdateNodeBounds, template/scene.h:855-865 -- checked bit for bit here), then
+// the nearer child's children on their own entries, in the reference's order and against the
+// same r.t: the visits are the binary walk's exactly.  A popped odd-depth child is addressed by
+// (its parent's record, half) and reads its children pair from that record.  Entry words: leaf
+// (node_word) as in the binary array, even-depth interior node (record << 8), odd
+// marker ((kQuadOdd | record << 1 | half) << 8).  false (no records) when a box is NaN, a parent is
+// not the exact union of its children (a caller's prebuilt tree), or the tree is too large.
+constexpr uint32_t kQuadOdd = 1u << 23;
+bool build_quads(const Bvh &b, const TreeWalk &w, const std::vector<uint8_t> &sticky, std::vector<float4> &rec,
+                 uint32_t &root_word) {
+    const Node *N = b.nodes.data();
+    if (b.nodes_used < 3 || N[0].count > 0) return false;
+    std::vector<int32_t> id(b.nodes_used, -1);
+    std::vector<uint32_t> order;
+    for (uint32_t k : w.order)   // pre-order, even-depth interior nodes numbered as met
+        if (N[k].count == 0 && !(w.depth[k] & 1u)) { id[k] = (int32_t)order.size(); order.push_back(k); }
+    if (order.size() >= (kQuadOdd >> 1)) return false;
+    // the union of two floats as the device's fminf / fmaxf gives it, or fail on NaN / +-0 ties
+    auto pick = [&](float a, float c, bool mn, float want) {
+        if (a != a || c != c || want != want) return false;
+        if (a == c && fbits(a) != fbits(c)) return false;
+        const float u = mn ? (a < c ? a : c) : (a > c ? a : c);
+        return fbits(u) == fbits(want);
+    };
+    auto entry = [&](uint32_t g, float4 *q) {
+        const Node &nd = N[g];
+        const uint32_t word = nd.count > 0 ? node_word(nd.leftFirst, nd.count) : ((uint32_t)id[g] << 8);
+        node_pack(mk(nd.mn[0], nd.mn[1], nd.mn[2]), mk(nd.mx[0], nd.mx[1], nd.mx[2]), word, 0.0f, q);
+    };
+    // the .w word of each entry: bit 0 (first slot of a half) the child is a leaf and this its entry,
+    // bit 1 this entry's node is sticky (mark_sticky), bit 2 (first slot) the child itself is sticky
+    rec.assign(8 * order.size(), make_float4(0, 0, 0, 0));
+    for (size_t r = 0; r < order.size(); ++r) {
+        const Node &x = N[order[r]];
+        for (uint32_t h = 0; h < 2; ++h) {
+            const uint32_t c = x.leftFirst + h;
+            float4 *q = &rec[8 * r + 4 * h];
+            const Node &cn = N[c];
+            const uint32_t sc = sticky[c] ? 6u : 0u;
+            if (cn.count > 0) {
+                entry(c, q);
+                q[1].w = ubits(1u | sc);
+                continue;
+            }
+            const Node &g1 = N[cn.leftFirst], &g2 = N[cn.leftFirst + 1];
+            for (int a = 0; a < 3; ++a)
+                if (!pick(g1.mn[a], g2.mn[a], true, cn.mn[a]) || !pick(g1.mx[a], g2.mx[a], false, cn.mx[a])) return false;
+            entry(cn.leftFirst, q);
+            entry(cn.leftFirst + 1, q + 2);
+            q[1].w = ubits((sticky[cn.leftFirst] ? 2u : 0u) | (sc & 4u));
+            q[3].w = ubits(sticky[cn.leftFirst + 1] ? 2u : 0u);
+        }
+    }
+    root_word = (uint32_t)id[0] << 8;
+    return true;
+}
+
+int material_flag(const rt_material &m, float diffuse, float specular) {   // getFlag overrides
+    switch (m.kind) {
+    case RT_DIFFUSE: return F_DIFFUSE;
+    case RT_MIRROR: return F_SPECULAR;
+    case RT_DIELECTRIC: return F_DIELECTRIC;
+    case RT_LIGHT: return F_LIGHT;
+    default:
+        if (diffuse < kFLT_EPSILON) return F_SPECULAR;
+        if (specular < kFLT_EPSILON) return F_DIFFUSE;
+        return F_MIX;
+    }
+}
+
+constexpr uint32_t kMaxNodes = 1u << 24;   // the packed word's leftFirst field is 24 bits wide
+
+// a caller's prebuilt tree: the indices a permutation, the walk in range, child pairs even
+int validate_bvh(const Bvh &b, uint32_t n, TreeWalk &w) {
+    if (b.nodes_used < 2 || b.nodes_used > b.nodes.size()) return fail(RT_ERR_INVALID, "BVH node count out of range");
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (b.indices[i] >= n || seen[b.indices[i]]) return fail(RT_ERR_INVALID, "BVH indices are not a permutation");
+        seen[b.indices[i]] = 1;
+    }
+    switch (walk_tree(b.nodes.data(), b.nodes_used, n, w)) {
+    case kTreeCycle: return fail(RT_ERR_INVALID, "BVH has a cycle");
+    case kTreeLeafRange: return fail(RT_ERR_INVALID, "BVH leaf outside the index array");
+    case kTreeChildRange: return fail(RT_ERR_INVALID, "BVH child pair out of range / misaligned");
+    }
+    for (uint32_t k : w.order)
+        if (b.nodes[k].count == 0 && (b.nodes[k].leftFirst & 1u))
+            return fail(RT_ERR_INVALID, "BVH child pair out of range / misaligned");
+    return RT_OK;
+}
+
+inline const float *transform_of(const rt_scene_desc *d, uint32_t id) {
+    return d->transforms ? d->transforms + 16 * (size_t)id : nullptr;
+}
+
+inline f3 tvec_host(float4 r0, float4 r1, float4 r2, f3 a) {
+    const float M[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+    return tvec(M, a);
+}
+
+// ---------------------------------------------------------------- the steps of pack_scene, in order
+
+int check_description(const rt_scene_desc *d, ScenePack &s) {
+    if (!d || !d->prims || d->num_prims == 0 || !d->materials || d->num_materials == 0)
+        return fail(RT_ERR_INVALID, "rt_scene_create: empty or null description");
+    const uint32_t n = d->num_prims;
+    if (n >= (1u << 24)) return fail(RT_ERR_UNSUPPORTED, "more than 2^24 primitives");
+    for (uint32_t i = 0; i < n; ++i) {
+        const rt_prim &p = d->prims[i];
+        if (p.type < RT_SPHERE || p.type > RT_TRIANGLE)
+            return fail(RT_ERR_INVALID, "primitive " + std::to_string(i) + ": unknown type");
+        if (p.material < 0 || (uint32_t)p.material >= d->num_materials)
+            return fail(RT_ERR_INVALID, "primitive " + std::to_string(i) + ": material out of range");
+    }
+    if (d->prims[0].type != RT_SPHERE && d->prims[0].type != RT_QUAD)
+        return fail(RT_ERR_UNSUPPORTED, "primitive 0 must be the light, a sphere or a quad (Scene::GetRandomLight returns 0)");
+    for (uint32_t i = 0; i < d->num_materials; ++i) {
+        const rt_material &m = d->materials[i];
+        if (m.kind < RT_DIFFUSE || m.kind > RT_TEXTURE) return fail(RT_ERR_INVALID, "unknown material kind");
+        if (m.kind == RT_TEXTURE && (m.texture < 0 || (uint32_t)m.texture >= d->num_textures || !d->textures))
+            return fail(RT_ERR_INVALID, "material " + std::to_string(i) + ": texture index out of range");
+    }
+    for (uint32_t i = 0; i < d->num_textures; ++i)
+        if (!d->textures[i].pixels || !d->textures[i].width || !d->textures[i].height)
+            return fail(RT_ERR_INVALID, "texture " + std::to_string(i) + " is empty");
+    // needs the kext kernels: cubes, quads, textures, a light material other than the core four
+    s.ext = d->prims[0].type == RT_QUAD;
+    {
+        const int lk = d->materials[d->prims[0].material].kind;
+        s.ext = s.ext || !(lk == RT_LIGHT || lk == RT_DIFFUSE || lk == RT_MIRROR || lk == RT_DSMIX);
+    }
+    for (uint32_t i = 0; i < n && !s.ext; ++i) s.ext = d->prims[i].type == RT_CUBE || d->prims[i].type == RT_QUAD;
+    for (uint32_t i = 0; i < d->num_materials && !s.ext; ++i) s.ext = d->materials[i].kind == RT_TEXTURE;
+    if (d->sky_pixels) {
+        uint32_t w = d->sky_width, h = d->sky_height;
+        if (!w || !h || (w & (w - 1)) || (h & (h - 1)))
+            return fail(RT_ERR_INVALID, "sky texture must have power-of-two sides (renderer.h:18)");
+    }
+    // interior nodes store a node index in the 24-bit leftFirst field of the packed device
+    // word (node_word): trees with more than 2^24 nodes cannot be addressed
+    if (d->bvh_nodes && d->bvh_num_nodes > kMaxNodes)
+        return fail(RT_ERR_UNSUPPORTED, "prebuilt BVH with more than 2^24 nodes (24-bit child index)");
+    if (d->bvh_kind != RT_BVH_PLAIN && d->bvh_kind != RT_BVH_SBVH) return fail(RT_ERR_INVALID, "unknown bvh_kind");
+    return RT_OK;
+}
+
+// the tree: prebuilt (validated; depth and widest leaf measured) or built here, and its walk
+int take_tree(const rt_scene_desc *d, const PackOptions &o, ScenePack &s, TreeWalk &w) {
+    const uint32_t n = d->num_prims;
+    Bvh &b = s.bvh;
+    int rc;
+    if (d->bvh_nodes) {
+        if (!d->bvh_indices || d->bvh_num_nodes < 2) return fail(RT_ERR_INVALID, "prebuilt BVH incomplete");
+        b.nodes.resize(d->bvh_num_nodes);
+        std::memcpy(b.nodes.data(), d->bvh_nodes, sizeof(Node) * d->bvh_num_nodes);
+        b.indices.assign(d->bvh_indices, d->bvh_indices + n);
+        b.nodes_used = d->bvh_num_nodes;
+        if ((rc = validate_bvh(b, n, w)) != RT_OK) return rc;
+        // depth as Scene::maxDepthBVH (template/scene.h:144-154): interior levels, root leaf = 1
+        b.max_leaf = w.max_leaf;
+        for (uint32_t k : w.order)
+            if (b.nodes[k].count > 0) b.depth = std::max(b.depth, k == 0 ? 1u : w.depth[k]);
+    } else {
+        // the option picks the tree only where the caller left the default
+        const int kind = d->bvh_kind == RT_BVH_PLAIN ? o.bvh_kind : d->bvh_kind;
+        if ((rc = (kind == RT_BVH_SBVH ? build_sbvh : build_bvh)(d->prims, d->transforms, n, b)) != RT_OK) return rc;
+        if (walk_tree(b.nodes.data(), b.nodes_used, b.indices.size(), w) != kTreeOk)
+            return fail(RT_ERR_INVALID, "the builder's tree does not walk");
+    }
+    if (b.nodes_used > kMaxNodes) return fail(RT_ERR_UNSUPPORTED, "BVH with more than 2^24 nodes (24-bit child index)");
+    if (b.max_leaf > 255) return fail(RT_ERR_UNSUPPORTED, "BVH leaf with more than 255 primitives");
+    if (b.depth > 64) return fail(RT_ERR_UNSUPPORTED, "BVH deeper than 64 (the reference's stack[64])");
+    s.stack_depth = pick_stack(b.depth);
+    // trees deeper than 60: the lane stacks (depth x 1 KB) leave no room for the walk's words
+    s.walk_fits = (size_t)s.stack_depth * (256u + 4u) * sizeof(uint32_t) <= kLdsLaunchMax;
+    return RT_OK;
+}
+
+// The wave camera walk's sticky boxes (rt_kernels.inc, wave_closest_hit_fast): a node with a
+// primitive below it whose computed t can lie well before its leaf box's entry -- a sliver
+// triangle (tri_sliver: its smallest corner angle's sine under 2^RT_WALK_STICKY, default 2^-8), a
+// sphere (t = -b - sqrt(d) near a tangent, Primitive.h:150-177) or a quad -- is sticky, and so is
+// every ancestor; the walk culls it only on a slab miss (walk_word).  prim_flag: per primitive.
+void mark_sticky(const Bvh &b, const TreeWalk &w, const rt_scene_desc *d, const PackOptions &o,
+                 std::vector<uint8_t> &sticky, std::vector<uint8_t> &prim_flag) {
+    prim_flag.resize(d->num_prims);
+    for (uint32_t i = 0; i < d->num_prims; ++i) {
+        const rt_prim &p = d->prims[i];
+        // planes and cubes never: a plane's box is unbounded and entered from inside
+        if (p.type == RT_SPHERE || p.type == RT_QUAD) prim_flag[i] = o.sticky_spheres;
+        else prim_flag[i] = p.type == RT_TRIANGLE && tri_sliver(p.v, o.sliver_lim);
+    }
+    sticky.assign(b.nodes_used, 0);
+    for (uint32_t i : w.order) {
+        const Node &nd = b.nodes[i];
+        bool st = false;
+        for (uint32_t k = nd.leftFirst; k < nd.leftFirst + nd.count && !st; ++k) st = prim_flag[b.indices[k]] != 0;
+        for (uint32_t j = i; st && j != ~0u && !sticky[j]; j = w.parent[j]) sticky[j] = 1;
+    }
+}
+
+// the device node array, and what a refit needs of every primitive
+void pack_nodes(const rt_scene_desc *d, const PackOptions &o, const std::vector<uint8_t> &sticky, ScenePack &s) {
+    s.nodes.resize(2 * (size_t)s.bvh.nodes_used);
+    for (uint32_t i = 0; i < s.bvh.nodes_used; ++i) {
+        const Node &nd = s.bvh.nodes[i];
+        node_pack(mk(nd.mn[0], nd.mn[1], nd.mn[2]), mk(nd.mx[0], nd.mx[1], nd.mx[2]), node_word(nd.leftFirst, nd.count),
+                  walk_word(sticky[i] != 0, o.walk_margin), &s.nodes[2 * (size_t)i]);
+    }
+    const uint32_t n = d->num_prims;
+    s.pbox.resize(6 * (size_t)n);
+    s.boxes_finite = true;
+    for (uint32_t id = 0; id < n; ++id) {
+        PrimX x;
+        PrimGeom g;
+        prim_transform(d->prims[id], transform_of(d, id), x);
+        prim_geometry(d->prims[id], x, g);
+        const float bx[6] = {g.bmin.x, g.bmin.y, g.bmin.z, g.bmax.x, g.bmax.y, g.bmax.z};
+        for (int c = 0; c < 6; ++c) {
+            s.pbox[6 * (size_t)id + c] = bx[c];
+            if (!std::isfinite(bx[c])) s.boxes_finite = false;
+        }
+        s.pinfo[id] = (uint8_t)(d->prims[id].type | (s.pinfo[id] ? 0x80 : 0));
+    }
+}
+
+// cubes and quads keep their matrices and data in a side table (8 float4 each); xindex: per id
+void pack_xprims(const rt_scene_desc *d, ScenePack &s, std::vector<uint32_t> &xindex) {
+    std::vector<float4> &xprims = s.xprims;
+    xindex.assign(d->num_prims, 0);
+    s.has_cubes = false;
+    for (uint32_t id = 0; id < d->num_prims; ++id) {
+        const rt_prim &p = d->prims[id];
+        if (p.type != RT_CUBE && p.type != RT_QUAD) continue;
+        if (p.type == RT_CUBE) s.has_cubes = true;
+        PrimX x;
+        prim_transform(p, transform_of(d, id), x);
+        xindex[id] = (uint32_t)(xprims.size() / 8);
+        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.Minv[4 * r], x.Minv[4 * r + 1], x.Minv[4 * r + 2], x.Minv[4 * r + 3]));
+        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.M[4 * r], x.M[4 * r + 1], x.M[4 * r + 2], x.M[4 * r + 3]));
+        if (p.type == RT_CUBE) {   // data[0] = -0.5 size, data[1] = 0.5 size (Primitive.h:724-725)
+            const f3 sz = mk(p.v[3], p.v[4], p.v[5]), a = -0.5f * sz, b = 0.5f * sz;
+            xprims.push_back(make_float4(a.x, a.y, a.z, 0.0f));
+            xprims.push_back(make_float4(b.x, b.y, b.z, 0.0f));
+        } else {                   // data[0].x = 0.5 size (Primitive.h:737)
+            xprims.push_back(make_float4(0.5f * p.v[0], 0.0f, 0.0f, 0.0f));
+            xprims.push_back(make_float4(0, 0, 0, 0));
+        }
+    }
+}
+
+// per-id shading records
+void pack_shade(const rt_scene_desc *d, const std::vector<uint32_t> &xindex, ScenePack &s) {
+    s.shade.resize(2 * (size_t)d->num_prims);
+    for (uint32_t id = 0; id < d->num_prims; ++id) {
+        const rt_prim &p = d->prims[id];
+        float4 s0, s1 = make_float4(ubits((uint32_t)p.type), 0, 0, 0);
+        if (p.type == RT_CUBE || p.type == RT_QUAD) {
+            const float4 *x = &s.xprims[8 * (size_t)xindex[id]];
+            // quad: constant normal TransformVector((0,-1,0), Transform) (Primitive.h:306-307)
+            f3 N = p.type == RT_QUAD ? tvec_host(x[3], x[4], x[5], mk(0, -1, 0)) : mk(0, 0, 0);
+            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
+            s1.z = ubits(xindex[id]);
+        } else if (p.type == RT_TRIANGLE) {
+            f3 N = tri_normal(p.v);
+            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
+        } else if (p.type == RT_SPHERE) {
+            float T[16];
+            translate_matrix(p.v[0], p.v[1], p.v[2], T);
+            f3 c = tpos(T, mk(0, 0, 0));
+            s0 = make_float4(c.x, c.y, c.z, ibits(p.material));
+            s1.y = 1.0f / p.v[3];                                      // data[0].z
+        } else {
+            s0 = make_float4(p.v[0], p.v[1], p.v[2], ibits(p.material));
+        }
+        s.shade[2 * id] = s0;
+        s.shade[2 * id + 1] = s1;
+    }
+}
+
+// leaf-order primitive records (an SBVH repeats primitives)
+void pack_slots(const rt_scene_desc *d, const std::vector<uint32_t> &xindex, ScenePack &s) {
+    const uint32_t nrefs = (uint32_t)s.bvh.indices.size();
+    s.prims.resize(3 * (size_t)nrefs);
+    for (uint32_t k = 0; k < nrefs; ++k) {
+        const uint32_t id = s.bvh.indices[k];
+        const rt_prim &p = d->prims[id];
+        float4 *q = &s.prims[3 * (size_t)k];
+        if (p.type == RT_TRIANGLE) {
+            tri_record(p.v, id, q);
+        } else if (p.type == RT_SPHERE) {
+            float T[16];
+            translate_matrix(p.v[0], p.v[1], p.v[2], T);
+            f3 c = tpos(T, mk(0, 0, 0));
+            float r = p.v[3];
+            q[0] = make_float4(c.x, c.y, c.z, ibits((int)id));
+            q[1] = make_float4(r * r, 0.0f, 0.0f, ubits(T_SPH)); // data[0].y
+            q[2] = make_float4(0, 0, 0, 0);
+        } else if (p.type == RT_PLANE) {
+            q[0] = make_float4(p.v[0], p.v[1], p.v[2], ibits((int)id));
+            q[1] = make_float4(p.v[3], 0.0f, 0.0f, ubits(T_PLANE));
+            q[2] = make_float4(0, 0, 0, 0);
+        } else {
+            q[0] = make_float4(0, 0, 0, ibits((int)id));
+            q[1] = make_float4(ubits(xindex[id]), 0.0f, 0.0f, ubits(p.type == RT_CUBE ? T_CUBE : T_QUAD));
+            q[2] = make_float4(0, 0, 0, 0);
+        }
+    }
+    if (s.xprims.empty()) s.xprims.push_back(make_float4(0, 0, 0, 0));
+}
+
+void pack_materials(const rt_scene_desc *d, ScenePack &s) {
+    std::vector<uint32_t> tex_offsets(d->num_textures, 0);   // where each starts in the concatenated texels
+    for (uint32_t i = 1; i < d->num_textures; ++i)
+        tex_offsets[i] = tex_offsets[i - 1] + d->textures[i - 1].width * d->textures[i - 1].height;
+    s.mats.resize(d->num_materials);
+    for (uint32_t i = 0; i < d->num_materials; ++i) {
+        const rt_material &m = d->materials[i];
+        DevMaterial &o = s.mats[i];
+        std::memset(&o, 0, sizeof(o));
+        o.kind = m.kind;
+        for (int c = 0; c < 3; ++c) { o.c0[c] = m.color[c]; o.c1[c] = m.color2[c]; }
+        o.ior = m.ior;
+        // Checkerboard.h:6-14, TextureMaterial.h:6-17 (short ctor: diffuse 1, specular 0),
+        // DSMix.h:6-9 (always clamped): clamp = fmaxf(a, fminf(f, b)), precomp.h:782
+        if (m.kind == RT_CHECKERBOARD || m.kind == RT_TEXTURE || m.kind == RT_DSMIX) {
+            if (m.diffuse < 0.0f && m.kind != RT_DSMIX) { o.diffuse = 1.0f; o.specular = 0.0f; }
+            else { o.diffuse = tmax(0.0f, tmin(m.diffuse, 1.0f)); o.specular = 1.0f - o.diffuse; }
+        }
+        if (m.kind == RT_TEXTURE) {
+            const rt_texture &t = d->textures[m.texture];
+            o.tex_off = tex_offsets[m.texture];
+            o.tex_w = t.width; o.tex_h = t.height;
+        }
+        o.flag = material_flag(m, o.diffuse, o.specular);
+    }
+}
+
+// textures, concatenated, and the sky
+void pack_sky_and_textures(const rt_scene_desc *d, ScenePack &s) {
+    for (uint32_t i = 0; i < d->num_textures; ++i) {
+        const rt_texture &t = d->textures[i];
+        s.texels.insert(s.texels.end(), t.pixels, t.pixels + (size_t)t.width * t.height);
+    }
+    if (s.texels.empty()) s.texels.push_back(0);
+    SceneView &v = s.view;
+    v.sky_w = 1024; v.sky_h = 512;
+    if (d->sky_pixels) {
+        v.sky_w = d->sky_width; v.sky_h = d->sky_height;
+        s.sky.assign(d->sky_pixels, d->sky_pixels + (size_t)v.sky_w * v.sky_h);
+    } else {
+        s.sky.assign((size_t)v.sky_w * v.sky_h, 0x406080u);
+    }
+    const uint32_t p = s.sky[0];
+    v.sky_const = std::all_of(s.sky.begin(), s.sky.end(), [&](uint32_t t) { return t == p; }) ? 1 : 0;
+    f3 c = mk((float)((p >> 16) & 255), (float)((p >> 8) & 255), (float)(p & 255)) * kSKY;
+    v.sky_rgb[0] = c.x; v.sky_rgb[1] = c.y; v.sky_rgb[2] = c.z;
+}
+
+void fill_light(const rt_scene_desc *d, SceneView &v) {
+    const rt_prim &L = d->prims[0];
+    PrimX LX;
+    prim_transform(L, transform_of(d, 0), LX);
+    std::memcpy(v.light_M, LX.M, sizeof(v.light_M));
+    f3 lc = tpos(LX.M, mk(0, 0, 0));
+    v.light_c[0] = lc.x; v.light_c[1] = lc.y; v.light_c[2] = lc.z;
+    v.light_mat = L.material;
+    v.light_quad = L.type == RT_QUAD;
+    if (v.light_quad) {
+        v.light_qsize = 0.5f * L.v[0];
+        const float side = 2.0f * v.light_qsize;                      // GetArea, Primitive.h:461-463
+        v.light_area = side * side;
+        const f3 N = tvec(LX.M, mk(0, -1, 0));
+        v.light_N[0] = N.x; v.light_N[1] = N.y; v.light_N[2] = N.z;
+    } else {
+        v.light_r = L.v[3];
+        v.light_r2 = L.v[3] * L.v[3];
+        v.light_invr = 1.0f / L.v[3];
+        v.light_area = 4.0f * kPI * v.light_r2;                        // Primitive.h:452
+    }
+}
+
+void tree_flags(ScenePack &s) {
+    const Bvh &b = s.bvh;
+    // every child box inside its parent's, compared as floats (the wave walk's pops and its leaf
+    // check rely on it: a child's slab entry is then never below its parent's)
+    s.nested = true;
+    for (uint32_t i = 0; i < b.nodes_used && s.nested; ++i) {
+        if (i == 1) continue;
+        const Node &nd = b.nodes[i];
+        if (nd.count > 0) continue;
+        for (uint32_t c = nd.leftFirst; c < nd.leftFirst + 2 && s.nested; ++c) {
+            const Node &ch = b.nodes[c];
+            for (int a = 0; a < 3; ++a)
+                if (!(ch.mn[a] >= nd.mn[a]) || !(ch.mx[a] <= nd.mx[a])) s.nested = false;
+        }
+    }
+    s.view.bounds_finite = 1;
+    for (uint32_t i = 0; i < b.nodes_used && s.view.bounds_finite; ++i) {
+        if (i == 1) continue;
+        const Node &nd = b.nodes[i];
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(nd.mn[c]) || !std::isfinite(nd.mx[c])) s.view.bounds_finite = 0;
+    }
+}
+
+}  // namespace
+
+int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &s) {
+    s = ScenePack();
+    int rc = check_description(d, s);
+    if (rc != RT_OK) return rc;
+    TreeWalk w;
+    if ((rc = take_tree(d, o, s, w)) != RT_OK) return rc;
+    std::vector<uint8_t> sticky;
+    std::vector<uint32_t> xindex;
+    mark_sticky(s.bvh, w, d, o, sticky, s.pinfo);
+    pack_nodes(d, o, sticky, s);
+    SceneView &v = s.view;
+    v.walk_margin = o.walk_margin;
+    s.has_quads = o.quads && build_quads(s.bvh, w, sticky, s.quads, v.quad_root);
+    pack_xprims(d, s, xindex);
+    pack_shade(d, xindex, s);
+    pack_slots(d, xindex, s);
+    pack_materials(d, s);
+    pack_sky_and_textures(d, s);
+    fill_light(d, v);
+    v.root_word = node_word(s.bvh.nodes[0].leftFirst, s.bvh.nodes[0].count);
+    v.stack_entries = s.stack_depth;
+    tree_flags(s);
+    return RT_OK;
+}
+
+}  // namespace rt

@@ -220,9 +220,9 @@ def grazing_cameras(rt, W, H):
 
 
 def sticky_prims(rt, prims, log2_lim=-8):
-    """The primitives whose boxes the wave camera walk never culls by distance (rt_device.hip
-    mark_sticky): spheres, quads and sliver triangles (smallest corner angle's sine under
-    2^log2_lim, from the float vertices in double)."""
+    """The primitives whose boxes the wave camera walk never culls by distance (rt_scene_pack.cpp
+    mark_sticky, rt_records.h tri_sliver): spheres, quads and sliver triangles (smallest corner
+    angle's sine under 2^log2_lim, from the float vertices in double)."""
     out = np.zeros(len(prims), bool)
     lim = 2.0 ** log2_lim
     for i, p in enumerate(prims):
