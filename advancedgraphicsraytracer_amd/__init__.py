@@ -48,6 +48,11 @@ class Prim(C.Structure):
     _fields_ = [("type", C.c_int32), ("material", C.c_int32), ("v", C.c_float * 9)]
 
 
+class TriXform(C.Structure):
+    """rt_tri_xform: triangles [first, first + count) moved by the mat4 M"""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("M", C.c_float * 16)]
+
+
 class Material(C.Structure):
     _fields_ = [("kind", C.c_int32), ("color", C.c_float * 3), ("color2", C.c_float * 3), ("ior", C.c_float),
                 ("diffuse", C.c_float), ("texture", C.c_int32)]
@@ -127,6 +132,9 @@ def lib():
         "rt_bvh_refit_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, vp, u32, C.POINTER(u32)], C.c_int),
         "rt_scene_update_triangles": ([vp, u32, u32, vp, vp], C.c_int),
         "rt_scene_update_triangles_host": ([vp, u32, u32, fp], C.c_int),
+        "rt_scene_update_prims": ([vp, u32, u32, vp, vp, vp], C.c_int),
+        "rt_scene_update_prims_host": ([vp, u32, u32, C.POINTER(Prim), fp], C.c_int),
+        "rt_scene_transform_triangles": ([vp, C.POINTER(TriXform), u32, vp, vp], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -296,6 +304,18 @@ def _transforms(prims):
         if getattr(p, "T", None) is not None:
             T[i] = np.asarray(p.T, np.float32).reshape(16)
     return T
+
+
+def pack_prims(prims):
+    """Prim records as arrays: (records [n, 11] int32 -- type, material and the bits of v[0..8] --,
+    transforms [n, 16] float32 with each record's .T, identity where it has none): the layout
+    Scene.update_prims takes as device tensors."""
+    arr = (Prim * len(prims))(*prims)
+    rec = np.frombuffer(bytes(arr), np.int32).reshape(len(prims), 11).copy()
+    T = _transforms(prims)
+    if T is None:
+        T = np.tile(np.eye(4, dtype=np.float32).reshape(16), (len(prims), 1))
+    return rec, T
 
 
 def build_bvh_host(prims):
@@ -524,6 +544,53 @@ class Scene:
             return
         v = np.ascontiguousarray(verts.numpy() if isinstance(verts, torch.Tensor) else verts, np.float32).reshape(-1, 9)
         _check(self.L.rt_scene_update_triangles_host(self.h, first, len(v), _fptr(v)))
+
+    def update_prims(self, first, prims, stream=None):
+        """rt_scene_update_prims: new records for primitives [first, first + count) of any kind (types and
+        materials as the scene holds them) and an in-place BVH refit -- Primitive::UpdateTransform /
+        Scene::SetTime.  prims: a list of sphere() / plane() / cube() / quad() / triangle() records, whose
+        .T is honoured; or a pair of torch tensors on the scene's device, (records [count, 11] int32 or
+        float32 words, transforms [count, 16] float32 or None), as pack_prims lays them out.  Moves the
+        light when the range holds primitive 0.  Blocks; render the next frame with reset=True."""
+        torch = _torch()
+        if isinstance(prims, (tuple, list)) and len(prims) == 2 and isinstance(prims[0], torch.Tensor):
+            rec, T = prims
+            if not rec.is_cuda or rec.device.index != self.device or (T is not None and (not T.is_cuda or T.device.index != self.device)):
+                raise RTError(RT_ERR_INVALID, "update_prims: tensors must be on the scene's device")
+            if rec.element_size() != 4 or rec.dim() != 2 or rec.shape[1] != 11:
+                raise RTError(RT_ERR_INVALID, "update_prims: records must be [count, 11] 32-bit words")
+            rec = rec.contiguous()
+            if T is not None:
+                T = T.to(dtype=torch.float32).contiguous().reshape(-1, 16)
+                if T.shape[0] != rec.shape[0]:
+                    raise RTError(RT_ERR_INVALID, "update_prims: one transform per record")
+            s = stream if stream is not None else torch.cuda.current_stream(rec.device).cuda_stream
+            _check(self.L.rt_scene_update_prims(self.h, first, rec.shape[0], C.c_void_p(rec.data_ptr()),
+                                                None if T is None else C.c_void_p(T.data_ptr()), C.c_void_p(s)))
+            return
+        prims = list(prims)
+        arr = (Prim * len(prims))(*prims)
+        T = _transforms(prims)
+        _check(self.L.rt_scene_update_prims_host(self.h, first, len(prims), arr, None if T is None else _fptr(T)))
+
+    def transform_triangles(self, ranges, rest, stream=None):
+        """rt_scene_transform_triangles: ranges = [(first, count, M)] -- disjoint runs of triangle
+        primitives, any order, each with its mat4 (16 floats) --; rest = their object-space vertices
+        [total, 9] (or [total, 3, 3]) float32, the ranges back to back, a torch tensor on the scene's
+        device or a numpy array (uploaded).  World vertices are TransformPosition(rest, M) as
+        mesh_to_prims computes them; one call moves every range and refits once."""
+        torch = _torch()
+        arr = (TriXform * len(ranges))()
+        for k, (f, n, M) in enumerate(ranges):
+            arr[k].first, arr[k].count = int(f), int(n)
+            arr[k].M[:] = [float(x) for x in np.asarray(M, np.float32).reshape(16)]
+        if not isinstance(rest, torch.Tensor):
+            rest = torch.from_numpy(np.ascontiguousarray(rest, np.float32))
+        v = rest.to(device=f"cuda:{self.device}", dtype=torch.float32).contiguous().reshape(-1, 9)
+        if v.shape[0] != sum(int(n) for _, n, _ in ranges):
+            raise RTError(RT_ERR_INVALID, "transform_triangles: rest must hold 9 floats per triangle of the ranges")
+        s = stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
+        _check(self.L.rt_scene_transform_triangles(self.h, arr, len(ranges), C.c_void_p(v.data_ptr()), C.c_void_p(s)))
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

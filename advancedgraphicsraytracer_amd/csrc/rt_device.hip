@@ -121,6 +121,8 @@ struct rt_scene {
     RefitPlan plan;
     void *d_slot_of = nullptr, *d_slot_box = nullptr, *d_list = nullptr, *d_lvl = nullptr, *d_grp = nullptr, *d_flag = nullptr;
     bool bvh_stale = false;         // the device boxes are newer than bvh.nodes (rt_scene_copy_bvh downloads them)
+    void *d_ranges = nullptr;       // rt_scene_transform_triangles' range table (first, prefix counts, matrices)
+    size_t ranges_bytes = 0;
 };
 
 // renderer streams: up to 8 -- frames in flight of overlapped primary+shadow frames (timed
@@ -251,7 +253,7 @@ void free_scene(rt_scene *s) {
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
     void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads,
-                    s->d_slot_of, s->d_slot_box, s->d_list, s->d_lvl, s->d_grp, s->d_flag};
+                    s->d_slot_of, s->d_slot_box, s->d_list, s->d_lvl, s->d_grp, s->d_flag, s->d_ranges};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -1529,18 +1531,7 @@ static int ensure_refit(rt_scene *s) {
     return RT_OK;
 }
 
-static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st) {
-    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
-    int rc = ensure_refit(s);
-    if (rc != RT_OK) return rc;
-    // the finite check is a pass of its own, read back before anything is written
-    uint32_t bad = 0;
-    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
-    launch_check_finite(verts_dev, 9u * count, (uint32_t *)s->d_flag, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: a vertex is NaN or infinite");
+static RefitArgs refit_args(const rt_scene *s) {
     RefitArgs A{};
     A.nodes = (float4 *)s->d_nodes; A.prims = (float4 *)s->d_prims; A.shade = (float4 *)s->d_shade;
     A.slot_box = (float4 *)s->d_slot_box;
@@ -1548,7 +1539,11 @@ static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const f
     A.lvl = (const uint32_t *)s->d_lvl; A.grp = (const uint32_t *)s->d_grp;
     A.margin = s->view.walk_margin;
     A.sliver_lim = s->sliver_lim;
-    launch_update_tris(A, first, count, verts_dev, st);
+    return A;
+}
+
+// after an update kernel on `st`: the refit, then the scene's flags from the new root box
+static int refit_and_settle(rt_scene *s, const RefitArgs &A, hipStream_t st) {
     launch_refit(A, s->plan.ntreelets, s->plan.has_top, st);
     HIP_TRY(hipGetLastError());
     s->bvh_stale = true;
@@ -1561,6 +1556,92 @@ static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const f
     s->view.bounds_finite = finite ? 1 : 0;
     if (finite) s->nested = true;   // every box is now the union of finite boxes below it
     return RT_OK;
+}
+
+static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
+    int rc = ensure_refit(s);
+    if (rc != RT_OK) return rc;
+    // the finite check is a pass of its own, read back before anything is written
+    uint32_t bad = 0;
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
+    launch_check_finite(verts_dev, 9u * count, (uint32_t *)s->d_flag, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: a vertex is NaN or infinite");
+    const RefitArgs A = refit_args(s);
+    launch_update_tris(A, first, count, verts_dev, st);
+    return refit_and_settle(s, A, st);
+}
+
+// an in-place update needs a plain tree (every primitive in one leaf) with the binary node array alone
+static int refit_supported(const rt_scene *s, const char *who) {
+    if (s->bvh.indices.size() != s->num_prims)
+        return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": an SBVH scene (leaves share primitives) cannot be refitted");
+    if (s->quads) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": scene built with two-level node records (RT_PT_QUADS=1)");
+    return RT_OK;
+}
+
+static int update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
+                        hipStream_t st) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
+    int rc = ensure_refit(s);
+    if (rc != RT_OK) return rc;
+    // validation is a pass of its own, its flag read back before anything is written; the light's
+    // record and matrix come back with it
+    uint32_t bad = 0;
+    rt_prim light{};
+    float lightT[16];
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
+    launch_check_prims((const float4 *)s->d_shade, first, count, prims_dev, transforms_dev, (uint32_t *)s->d_flag, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    if (first == 0) {
+        HIP_TRY(hipMemcpyAsync(&light, prims_dev, sizeof(light), hipMemcpyDeviceToHost, st));
+        if (transforms_dev) HIP_TRY(hipMemcpyAsync(lightT, transforms_dev, sizeof(lightT), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad)
+        return fail(RT_ERR_INVALID, "rt_scene_update_prims: a record's type or material is not the scene's, or a field, "
+                                    "transform or box is NaN or infinite");
+    const RefitArgs A = refit_args(s);
+    launch_update_prims(A, (float4 *)s->d_xprims, first, count, prims_dev, transforms_dev, st);
+    // SceneView travels by value with every launch (renderers and the multi-GPU frames read
+    // s->view per frame), so the light's fields change here and nowhere else
+    if (first == 0) fill_light(light, transforms_dev ? lightT : nullptr, s->view);
+    return refit_and_settle(s, A, st);
+}
+
+static int transform_triangles(rt_scene *s, const std::vector<uint32_t> &tab, uint32_t nr, uint32_t total,
+                               const float *rest_dev, hipStream_t st) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene; the range table of an earlier call
+    int rc = ensure_refit(s);
+    if (rc != RT_OK) return rc;
+    const size_t need = sizeof(uint32_t) * tab.size();
+    if (need > s->ranges_bytes) {
+        if (s->d_ranges) HIP_TRY(hipFree(s->d_ranges));
+        s->d_ranges = nullptr;
+        s->ranges_bytes = 0;
+        HIP_TRY(hipMalloc(&s->d_ranges, need));
+        s->ranges_bytes = need;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_ranges, tab.data(), need, hipMemcpyHostToDevice, st));
+    XformRanges R{};
+    R.first = (const uint32_t *)s->d_ranges;
+    R.pre = R.first + nr;
+    R.M = (const float *)(R.pre + nr + 1);
+    R.nr = nr;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
+    launch_check_xform(R, total, rest_dev, (uint32_t *)s->d_flag, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the table has left the host vector too
+    if (bad) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: a transformed vertex is NaN or infinite");
+    const RefitArgs A = refit_args(s);
+    launch_xform_tris(A, R, total, rest_dev, st);
+    return refit_and_settle(s, A, st);
 }
 
 int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream) {
@@ -1599,6 +1680,93 @@ int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, 
     }
     HIP_TRY(hipMemcpyAsync(s->d_scratch, verts, need, hipMemcpyHostToDevice, s->stream));
     return rt_scene_update_triangles(s, first, count, (const float *)s->d_scratch, s->stream);
+}
+
+static int ensure_scratch(rt_scene *s, size_t need) {
+    if (need <= s->scratch_bytes) return RT_OK;
+    if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
+    s->d_scratch = nullptr;
+    s->scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&s->d_scratch, need));
+    s->scratch_bytes = need;
+    return RT_OK;
+}
+
+int rt_scene_update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
+                          void *stream) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null scene");
+    if (count == 0) return RT_OK;
+    if (!prims_dev) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null records");
+    int rc = refit_supported(s, "rt_scene_update_prims");
+    if (rc != RT_OK) return rc;
+    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims: range outside the primitives");
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return update_prims(s, first, count, prims_dev, transforms_dev, (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_scene_update_prims: ") + e.what());
+    }
+}
+
+int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims, const float *transforms) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: null scene");
+    if (count == 0) return RT_OK;
+    if (!prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: null records");
+    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: range outside the primitives");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+    const size_t pbytes = (sizeof(rt_prim) * (size_t)count + 15u) & ~(size_t)15u, tbytes = transforms ? 64 * (size_t)count : 0;
+    int rc = ensure_scratch(s, pbytes + tbytes);
+    if (rc != RT_OK) return rc;
+    char *base = (char *)s->d_scratch;
+    HIP_TRY(hipMemcpyAsync(base, prims, sizeof(rt_prim) * (size_t)count, hipMemcpyHostToDevice, s->stream));
+    if (transforms) HIP_TRY(hipMemcpyAsync(base + pbytes, transforms, tbytes, hipMemcpyHostToDevice, s->stream));
+    return rt_scene_update_prims(s, first, count, (const rt_prim *)base, transforms ? (const float *)(base + pbytes) : nullptr,
+                                 s->stream);
+}
+
+int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
+                                 void *stream) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null scene");
+    if (num_ranges == 0) return RT_OK;
+    if (!ranges) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null ranges");
+    int rc = refit_supported(s, "rt_scene_transform_triangles");
+    if (rc != RT_OK) return rc;
+    try {
+        // the table: first[nr], prefix counts[nr + 1], matrices[16 nr] -- empty ranges dropped
+        std::vector<uint32_t> firsts, pre{0u}, mats;
+        std::vector<std::pair<uint32_t, uint32_t>> spans;
+        for (uint32_t r = 0; r < num_ranges; ++r) {
+            const rt_tri_xform &x = ranges[r];
+            if (x.count == 0) continue;
+            if ((uint64_t)x.first + x.count > s->num_prims)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: range " + std::to_string(r) + " outside the primitives");
+            if ((uint64_t)pre.back() + x.count > 0xffffffffull / 9u)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: too many triangles");
+            for (uint32_t id = x.first; id < x.first + x.count; ++id)
+                if ((s->pinfo[id] & 0x7f) != RT_TRIANGLE)
+                    return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: primitive " + std::to_string(id) + " is not a triangle");
+            firsts.push_back(x.first);
+            pre.push_back(pre.back() + x.count);
+            const uint32_t *m = reinterpret_cast<const uint32_t *>(x.M);
+            mats.insert(mats.end(), m, m + 16);
+            spans.push_back({x.first, x.count});
+        }
+        if (firsts.empty()) return RT_OK;
+        std::sort(spans.begin(), spans.end());
+        for (size_t k = 1; k < spans.size(); ++k)
+            if (spans[k - 1].first + spans[k - 1].second > spans[k].first)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: ranges overlap");
+        if (!rest_dev) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null rest vertices");
+        const uint32_t nr = (uint32_t)firsts.size(), total = pre.back();
+        std::vector<uint32_t> tab(firsts);
+        tab.insert(tab.end(), pre.begin(), pre.end());
+        tab.insert(tab.end(), mats.begin(), mats.end());
+        HIP_TRY(hipSetDevice(s->device));
+        return transform_triangles(s, tab, nr, total, rest_dev, (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_scene_transform_triangles: ") + e.what());
+    }
 }
 
 int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {

@@ -34,22 +34,16 @@ void set_error(const std::string &msg) { g_err = msg; }
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 // ------------------------------------------------------------------ mat4
-static void identity(float M[16]) { std::memset(M, 0, 64); M[0] = M[5] = M[10] = M[15] = 1.0f; }
-void translate_matrix(float x, float y, float z, float M[16]) { identity(M); M[3] = x; M[7] = y; M[11] = z; }
-static void mat_mul(const float *a, const float *b, float *out) {
-    float r[16];
-    for (int i = 0; i < 16; i += 4)
-        for (int j = 0; j < 4; ++j)
-            r[i + j] = (a[i + 0] * b[j + 0]) + (a[i + 1] * b[j + 4]) + (a[i + 2] * b[j + 8]) + (a[i + 3] * b[j + 12]);
-    std::memcpy(out, r, 64);
-}
+// identity, translation and product are rt_records.h's (the primitives' transforms use them on the device too)
+static void identity(float M[16]) { mat4_identity(M); }
+void translate_matrix(float x, float y, float z, float M[16]) { mat4_translate(x, y, z, M); }
+static void mat_mul(const float *a, const float *b, float *out) { mat4_mul(a, b, out); }
 static void mat_rotate(int axis, float a, float M[16]) {   // precomp.h:1007-1009
     identity(M);
     if (axis == 0) { M[5] = cosf(a); M[6] = -sinf(a); M[9] = sinf(a); M[10] = cosf(a); }
     else if (axis == 1) { M[0] = cosf(a); M[2] = sinf(a); M[8] = -sinf(a); M[10] = cosf(a); }
     else { M[0] = cosf(a); M[1] = -sinf(a); M[4] = sinf(a); M[5] = cosf(a); }
 }
-static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 // ------------------------------------------------------------------ OBJ (tinyobj restatement)
 namespace obj {
@@ -239,85 +233,6 @@ struct Reader {
     }
 };
 }  // namespace obj
-
-// ------------------------------------------------------------------ primitive geometry
-void fast_inverse(const float *c, float *r) {
-    std::memcpy(r, kIdentity, sizeof(kIdentity));
-    r[0] = c[0], r[1] = c[4], r[2] = c[8];
-    r[4] = c[1], r[5] = c[5], r[6] = c[9];
-    r[8] = c[2], r[9] = c[6], r[10] = c[10];
-    r[3] = -(c[3] * r[0] + c[7] * r[1] + c[11] * r[2]);
-    r[7] = -(c[3] * r[4] + c[7] * r[5] + c[11] * r[6]);
-    r[11] = -(c[3] * r[8] + c[7] * r[9] + c[11] * r[10]);
-}
-
-void prim_transform(const rt_prim &p, const float *T16, PrimX &x) {
-    const float *T = T16 ? T16 : kIdentity;
-    if (p.type == RT_SPHERE) {
-        translate_matrix(p.v[0], p.v[1], p.v[2], x.M);           // createSphere, Primitive.h:690-698
-    } else if (p.type == RT_CUBE) {                               // createCube, Primitive.h:717-728
-        const f3 pos = mk(p.v[0], p.v[1], p.v[2]);
-        if (length(pos) > kFLT_EPSILON) {
-            float Tr[16];
-            translate_matrix(pos.x, pos.y, pos.z, Tr);
-            mat_mul(T, Tr, x.M);
-        } else {
-            std::memcpy(x.M, T, sizeof(x.M));
-        }
-    } else if (p.type == RT_QUAD) {
-        std::memcpy(x.M, T, sizeof(x.M));
-    } else {
-        std::memcpy(x.M, kIdentity, sizeof(x.M));
-    }
-    fast_inverse(x.M, x.Minv);
-}
-
-// the 8 cube corners / 4 quad corners in GetAABBMin/Max's order (Primitive.h:325-341)
-static int box_corners(const rt_prim &p, const PrimX &x, f3 *c) {
-    if (p.type == RT_CUBE) {
-        const f3 a = -0.5f * mk(p.v[3], p.v[4], p.v[5]), b = 0.5f * mk(p.v[3], p.v[4], p.v[5]);
-        c[0] = tpos(x.M, a);
-        c[1] = tpos(x.M, mk(b.x, a.y, a.z));
-        c[2] = tpos(x.M, mk(a.x, b.y, a.z));
-        c[3] = tpos(x.M, mk(a.x, a.y, b.z));
-        c[4] = tpos(x.M, b);
-        c[5] = tpos(x.M, mk(a.x, b.y, b.z));
-        c[6] = tpos(x.M, mk(b.x, a.y, b.z));
-        c[7] = tpos(x.M, mk(b.x, b.y, a.z));
-        return 8;
-    }
-    const float sz = 0.5f * p.v[0];
-    c[0] = tpos(x.M, mk(-sz, 0, -sz));
-    c[1] = tpos(x.M, mk(-sz, 0, sz));
-    c[2] = tpos(x.M, mk(sz, 0, -sz));
-    c[3] = tpos(x.M, mk(sz, 0, sz));
-    return 4;
-}
-
-void prim_geometry(const rt_prim &p, const PrimX &x, PrimGeom &g) {
-    if (p.type == RT_CUBE || p.type == RT_QUAD) {
-        f3 c[8];
-        const int n = box_corners(p, x, c);
-        g.centroid = tpos(x.M, mk(0, 0, 0));                      // ctor leaves centroid 0
-        g.bmin = g.bmax = c[0];
-        for (int i = 1; i < n; ++i) { g.bmin = fmin3(g.bmin, c[i]); g.bmax = fmax3(g.bmax, c[i]); }
-    } else if (p.type == RT_SPHERE) {
-        f3 c = tpos(x.M, mk(0, 0, 0));
-        float r = p.v[3];
-        g.centroid = c;                       // centroid float3(0) through Transform
-        g.bmin = c - mk(r, r, r);
-        g.bmax = c + mk(r, r, r);
-    } else if (p.type == RT_PLANE) {
-        f3 n = mk(p.v[0], p.v[1], p.v[2]);
-        g.centroid = tpos(kIdentity, (-n) * p.v[3]);
-        g.bmin = mk(-1e30f, -1e30f, -1e30f);
-        g.bmax = mk(1e30f, 1e30f, 1e30f);
-    } else {
-        f3 d0 = mk(p.v[0], p.v[1], p.v[2]), d1 = mk(p.v[3], p.v[4], p.v[5]), d2 = mk(p.v[6], p.v[7], p.v[8]);
-        g.centroid = tpos(kIdentity, ((d0 + d1) + d2) / 3.0f);
-        tri_box(p.v, g.bmin, g.bmax);
-    }
-}
 
 // ------------------------------------------------------------------ BVH
 namespace {

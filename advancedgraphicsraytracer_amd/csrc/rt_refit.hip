@@ -12,6 +12,9 @@
 //                      heights, every interior node takes the union of its two children and the OR
 //                      of their sticky bits;
 //   k_refit_top        one workgroup, the same over the nodes above the cut.
+// Two more front ends feed the same refit: rt_scene_update_prims (k_check_prims, k_update_prims:
+// records of any kind, the light included) and rt_scene_transform_triangles (k_check_xform,
+// k_xform_tris: ranges of triangles from object-space vertices and one matrix per range).
 // Boxes go through global memory: the waves of a workgroup share their CU's vector L1, so what one
 // wave stored before the barrier another loads after it.  Nothing is handed from one workgroup to
 // another inside a launch (the XCDs' L2s are not coherent with each other, and a CU's L1 is not
@@ -97,6 +100,114 @@ __global__ void __launch_bounds__(256) k_update_tris(RefitArgs A, uint32_t first
     slot_box(mn, mx, tri_sliver(p, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
 }
 
+__device__ __forceinline__ bool finite_f(float f) { return (__float_as_uint(f) & kExpMask) != kExpMask; }
+__device__ __forceinline__ bool finite_f3(f3 a) { return finite_f(a.x) && finite_f(a.y) && finite_f(a.z); }
+
+// rt_scene_update_prims' validation, one lane per record: type and material as the scene holds them
+// (the shading record's words), every field its kind reads finite, its transform finite where one
+// is read (cubes and quads), its box finite.  Writes nothing but the flag.
+__global__ void __launch_bounds__(256) k_check_prims(const float4 *__restrict__ shade, uint32_t first, uint32_t count,
+                                                     const rt_prim *__restrict__ prims, const float *__restrict__ T,
+                                                     uint32_t *flag) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t id = first + i;
+    const rt_prim p = prims[i];
+    bool ok = (uint32_t)p.type == fbits(shade[2 * (size_t)id + 1].x) && (uint32_t)p.material == fbits(shade[2 * (size_t)id].w);
+    if (ok) {
+        const int nf = p.type == RT_TRIANGLE ? 9 : p.type == RT_CUBE ? 6 : p.type == RT_QUAD ? 1 : 4;
+        for (int k = 0; k < nf; ++k) ok = ok && finite_f(p.v[k]);
+        const float *Ti = (T && (p.type == RT_CUBE || p.type == RT_QUAD)) ? T + 16u * (size_t)i : nullptr;
+        for (int k = 0; Ti && k < 16; ++k) ok = ok && finite_f(Ti[k]);
+        PrimX x;
+        PrimGeom g;
+        prim_transform(p, Ti, x);
+        prim_geometry(p, x, g);
+        ok = ok && finite_f3(g.bmin) && finite_f3(g.bmax);
+    }
+    if (!ok) *flag = 1u;
+}
+
+// one lane per record: the leaf-slot record, the shading record (material word kept), a cube's or a
+// quad's side-table entry (through the index its shading record holds) and the slot box; the sticky
+// flag is tri_sliver's for a triangle and stays as it is for every other kind (mark_sticky's depends
+// on the kind alone)
+__global__ void __launch_bounds__(256) k_update_prims(RefitArgs A, float4 *__restrict__ xprims, uint32_t first,
+                                                      uint32_t count, const rt_prim *__restrict__ prims,
+                                                      const float *__restrict__ T) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t id = first + i, slot = A.slot_of[id];
+    const rt_prim p = prims[i];
+    const bool xf = p.type == RT_CUBE || p.type == RT_QUAD;
+    PrimX x;
+    PrimGeom g;
+    prim_transform(p, (T && xf) ? T + 16u * (size_t)i : nullptr, x);
+    prim_geometry(p, x, g);
+    const float4 old0 = A.shade[2 * (size_t)id], old1 = A.shade[2 * (size_t)id + 1];
+    const uint32_t xi = fbits(old1.z);
+    float4 s[2];
+    prim_shade(p, x, xi, s);
+    s[0].w = old0.w;
+    A.shade[2 * (size_t)id] = s[0];
+    A.shade[2 * (size_t)id + 1] = s[1];
+    prim_record(p, x, id, xi, A.prims + 3 * (size_t)slot);
+    if (xf) prim_xentry(p, x, xprims + 8 * (size_t)xi);
+    const bool sticky = p.type == RT_TRIANGLE ? tri_sliver(p.v, A.sliver_lim) : slot_sticky(A.slot_box[2 * (size_t)slot]);
+    slot_box(g.bmin, g.bmax, sticky, A.slot_box + 2 * (size_t)slot);
+}
+
+// rt_scene_transform_triangles.  Lane i of the back-to-back rest triangles finds its range by binary
+// search over the prefix counts (pre[r] = triangles before range r, pre[nr] = all of them).
+__device__ __forceinline__ uint32_t range_of(const uint32_t *__restrict__ pre, uint32_t nr, uint32_t i) {
+    uint32_t lo = 0, hi = nr;   // pre[lo] <= i < pre[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pre[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// world vertices = TransformPosition(rest, M) per vertex, as Scene::LoadModel places a mesh
+// (template/scene.h:185-191)
+__device__ __forceinline__ void xform_tri(const XformRanges &R, uint32_t i, const float *__restrict__ rest, float w[9],
+                                          uint32_t &id) {
+    const uint32_t r = range_of(R.pre, R.nr, i);
+    const float *M = R.M + 16u * (size_t)r;
+    const float *q = rest + 9u * (size_t)i;
+    for (int k = 0; k < 3; ++k) {
+        const f3 v = tpos(M, mk(q[3 * k], q[3 * k + 1], q[3 * k + 2]));
+        w[3 * k] = v.x; w[3 * k + 1] = v.y; w[3 * k + 2] = v.z;
+    }
+    id = R.first[r] + (i - R.pre[r]);
+}
+__global__ void __launch_bounds__(256) k_check_xform(XformRanges R, uint32_t total, const float *__restrict__ rest,
+                                                     uint32_t *flag) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    float w[9];
+    uint32_t id;
+    xform_tri(R, i, rest, w, id);
+    bool ok = true;
+    for (int k = 0; k < 9; ++k) ok = ok && finite_f(w[k]);
+    if (!ok) *flag = 1u;
+}
+__global__ void __launch_bounds__(256) k_xform_tris(RefitArgs A, XformRanges R, uint32_t total,
+                                                    const float *__restrict__ rest) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    float w[9];
+    uint32_t id;
+    xform_tri(R, i, rest, w, id);
+    const uint32_t slot = A.slot_of[id];
+    const f3 N = tri_normal(w);
+    A.shade[2 * (size_t)id] = make_float4(N.x, N.y, N.z, A.shade[2 * (size_t)id].w);
+    tri_record(w, id, A.prims + 3 * (size_t)slot);
+    f3 mn, mx;
+    tri_box(w, mn, mx);
+    slot_box(mn, mx, tri_sliver(w, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
+}
+
 __device__ __forceinline__ void refit_node(const RefitArgs &A, uint32_t k) {
     const uint32_t word = fbits(A.nodes[2 * (size_t)k + 1].z), cnt = word & 255u, lf = word >> 8;
     f3 mn, mx;
@@ -144,6 +255,26 @@ void launch_check_finite(const float *verts_dev, uint32_t n, uint32_t *flag_dev,
 
 void launch_update_tris(const RefitArgs &A, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st) {
     hipLaunchKernelGGL(k_update_tris, dim3((count + 255u) / 256u), dim3(256), 0, st, A, first, count, verts_dev);
+}
+
+void launch_check_prims(const float4 *shade, uint32_t first, uint32_t count, const rt_prim *prims_dev,
+                        const float *transforms_dev, uint32_t *flag_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_check_prims, dim3((count + 255u) / 256u), dim3(256), 0, st, shade, first, count, prims_dev,
+                       transforms_dev, flag_dev);
+}
+
+void launch_update_prims(const RefitArgs &A, float4 *xprims, uint32_t first, uint32_t count, const rt_prim *prims_dev,
+                         const float *transforms_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_update_prims, dim3((count + 255u) / 256u), dim3(256), 0, st, A, xprims, first, count, prims_dev,
+                       transforms_dev);
+}
+
+void launch_check_xform(const XformRanges &R, uint32_t total, const float *rest_dev, uint32_t *flag_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_check_xform, dim3((total + 255u) / 256u), dim3(256), 0, st, R, total, rest_dev, flag_dev);
+}
+
+void launch_xform_tris(const RefitArgs &A, const XformRanges &R, uint32_t total, const float *rest_dev, hipStream_t st) {
+    hipLaunchKernelGGL(k_xform_tris, dim3((total + 255u) / 256u), dim3(256), 0, st, A, R, total, rest_dev);
 }
 
 void launch_refit(const RefitArgs &A, uint32_t ntreelets, bool has_top, hipStream_t st) {

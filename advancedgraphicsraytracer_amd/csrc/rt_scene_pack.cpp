@@ -128,11 +128,6 @@ inline const float *transform_of(const rt_scene_desc *d, uint32_t id) {
     return d->transforms ? d->transforms + 16 * (size_t)id : nullptr;
 }
 
-inline f3 tvec_host(float4 r0, float4 r1, float4 r2, f3 a) {
-    const float M[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
-    return tvec(M, a);
-}
-
 // ---------------------------------------------------------------- the steps of pack_scene, in order
 
 int check_description(const rt_scene_desc *d, ScenePack &s) {
@@ -271,45 +266,19 @@ void pack_xprims(const rt_scene_desc *d, ScenePack &s, std::vector<uint32_t> &xi
         PrimX x;
         prim_transform(p, transform_of(d, id), x);
         xindex[id] = (uint32_t)(xprims.size() / 8);
-        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.Minv[4 * r], x.Minv[4 * r + 1], x.Minv[4 * r + 2], x.Minv[4 * r + 3]));
-        for (int r = 0; r < 3; ++r) xprims.push_back(make_float4(x.M[4 * r], x.M[4 * r + 1], x.M[4 * r + 2], x.M[4 * r + 3]));
-        if (p.type == RT_CUBE) {   // data[0] = -0.5 size, data[1] = 0.5 size (Primitive.h:724-725)
-            const f3 sz = mk(p.v[3], p.v[4], p.v[5]), a = -0.5f * sz, b = 0.5f * sz;
-            xprims.push_back(make_float4(a.x, a.y, a.z, 0.0f));
-            xprims.push_back(make_float4(b.x, b.y, b.z, 0.0f));
-        } else {                   // data[0].x = 0.5 size (Primitive.h:737)
-            xprims.push_back(make_float4(0.5f * p.v[0], 0.0f, 0.0f, 0.0f));
-            xprims.push_back(make_float4(0, 0, 0, 0));
-        }
+        xprims.resize(xprims.size() + 8);
+        prim_xentry(p, x, &xprims[8 * (size_t)xindex[id]]);
     }
 }
 
 // per-id shading records
 void pack_shade(const rt_scene_desc *d, const std::vector<uint32_t> &xindex, ScenePack &s) {
     s.shade.resize(2 * (size_t)d->num_prims);
+    PrimX x{};
     for (uint32_t id = 0; id < d->num_prims; ++id) {
         const rt_prim &p = d->prims[id];
-        float4 s0, s1 = make_float4(ubits((uint32_t)p.type), 0, 0, 0);
-        if (p.type == RT_CUBE || p.type == RT_QUAD) {
-            const float4 *x = &s.xprims[8 * (size_t)xindex[id]];
-            // quad: constant normal TransformVector((0,-1,0), Transform) (Primitive.h:306-307)
-            f3 N = p.type == RT_QUAD ? tvec_host(x[3], x[4], x[5], mk(0, -1, 0)) : mk(0, 0, 0);
-            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
-            s1.z = ubits(xindex[id]);
-        } else if (p.type == RT_TRIANGLE) {
-            f3 N = tri_normal(p.v);
-            s0 = make_float4(N.x, N.y, N.z, ibits(p.material));
-        } else if (p.type == RT_SPHERE) {
-            float T[16];
-            translate_matrix(p.v[0], p.v[1], p.v[2], T);
-            f3 c = tpos(T, mk(0, 0, 0));
-            s0 = make_float4(c.x, c.y, c.z, ibits(p.material));
-            s1.y = 1.0f / p.v[3];                                      // data[0].z
-        } else {
-            s0 = make_float4(p.v[0], p.v[1], p.v[2], ibits(p.material));
-        }
-        s.shade[2 * id] = s0;
-        s.shade[2 * id + 1] = s1;
+        if (p.type != RT_TRIANGLE) prim_transform(p, transform_of(d, id), x);   // a triangle's is the identity, unread
+        prim_shade(p, x, xindex[id], &s.shade[2 * (size_t)id]);
     }
 }
 
@@ -317,29 +286,12 @@ void pack_shade(const rt_scene_desc *d, const std::vector<uint32_t> &xindex, Sce
 void pack_slots(const rt_scene_desc *d, const std::vector<uint32_t> &xindex, ScenePack &s) {
     const uint32_t nrefs = (uint32_t)s.bvh.indices.size();
     s.prims.resize(3 * (size_t)nrefs);
+    PrimX x{};
     for (uint32_t k = 0; k < nrefs; ++k) {
         const uint32_t id = s.bvh.indices[k];
         const rt_prim &p = d->prims[id];
-        float4 *q = &s.prims[3 * (size_t)k];
-        if (p.type == RT_TRIANGLE) {
-            tri_record(p.v, id, q);
-        } else if (p.type == RT_SPHERE) {
-            float T[16];
-            translate_matrix(p.v[0], p.v[1], p.v[2], T);
-            f3 c = tpos(T, mk(0, 0, 0));
-            float r = p.v[3];
-            q[0] = make_float4(c.x, c.y, c.z, ibits((int)id));
-            q[1] = make_float4(r * r, 0.0f, 0.0f, ubits(T_SPH)); // data[0].y
-            q[2] = make_float4(0, 0, 0, 0);
-        } else if (p.type == RT_PLANE) {
-            q[0] = make_float4(p.v[0], p.v[1], p.v[2], ibits((int)id));
-            q[1] = make_float4(p.v[3], 0.0f, 0.0f, ubits(T_PLANE));
-            q[2] = make_float4(0, 0, 0, 0);
-        } else {
-            q[0] = make_float4(0, 0, 0, ibits((int)id));
-            q[1] = make_float4(ubits(xindex[id]), 0.0f, 0.0f, ubits(p.type == RT_CUBE ? T_CUBE : T_QUAD));
-            q[2] = make_float4(0, 0, 0, 0);
-        }
+        if (p.type != RT_TRIANGLE) prim_transform(p, transform_of(d, id), x);
+        prim_record(p, x, id, xindex[id], &s.prims[3 * (size_t)k]);
     }
     if (s.xprims.empty()) s.xprims.push_back(make_float4(0, 0, 0, 0));
 }
@@ -392,29 +344,6 @@ void pack_sky_and_textures(const rt_scene_desc *d, ScenePack &s) {
     v.sky_rgb[0] = c.x; v.sky_rgb[1] = c.y; v.sky_rgb[2] = c.z;
 }
 
-void fill_light(const rt_scene_desc *d, SceneView &v) {
-    const rt_prim &L = d->prims[0];
-    PrimX LX;
-    prim_transform(L, transform_of(d, 0), LX);
-    std::memcpy(v.light_M, LX.M, sizeof(v.light_M));
-    f3 lc = tpos(LX.M, mk(0, 0, 0));
-    v.light_c[0] = lc.x; v.light_c[1] = lc.y; v.light_c[2] = lc.z;
-    v.light_mat = L.material;
-    v.light_quad = L.type == RT_QUAD;
-    if (v.light_quad) {
-        v.light_qsize = 0.5f * L.v[0];
-        const float side = 2.0f * v.light_qsize;                      // GetArea, Primitive.h:461-463
-        v.light_area = side * side;
-        const f3 N = tvec(LX.M, mk(0, -1, 0));
-        v.light_N[0] = N.x; v.light_N[1] = N.y; v.light_N[2] = N.z;
-    } else {
-        v.light_r = L.v[3];
-        v.light_r2 = L.v[3] * L.v[3];
-        v.light_invr = 1.0f / L.v[3];
-        v.light_area = 4.0f * kPI * v.light_r2;                        // Primitive.h:452
-    }
-}
-
 void tree_flags(ScenePack &s) {
     const Bvh &b = s.bvh;
     // every child box inside its parent's, compared as floats (the wave walk's pops and its leaf
@@ -459,7 +388,7 @@ int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &s) {
     pack_slots(d, xindex, s);
     pack_materials(d, s);
     pack_sky_and_textures(d, s);
-    fill_light(d, v);
+    fill_light(d->prims[0], transform_of(d, 0), v);
     v.root_word = node_word(s.bvh.nodes[0].leftFirst, s.bvh.nodes[0].count);
     v.stack_entries = s.stack_depth;
     tree_flags(s);

@@ -218,11 +218,45 @@ int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
  *                       range, or a NaN / infinite vertex -- the scene is untouched (the vertices are
  *                       checked in a pass of their own before anything is written);
  *   RT_ERR_UNSUPPORTED  an SBVH scene (num_refs != num_prims), or one built with RT_PT_QUADS=1.
- * count == 0 is RT_OK and does nothing.  Moving spheres, quads, cubes or the light, and topology
- * changes, need a new scene. */
+ * count == 0 is RT_OK and does nothing.  Other kinds and the light move with rt_scene_update_prims,
+ * whole meshes by matrix with rt_scene_transform_triangles; topology changes need a new scene. */
 int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream);
 /* the same with the vertices in host memory (staged on the scene's private stream) */
 int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts);
+/* Primitives of any kind in place (Primitive::UpdateTransform, Primitive.h:56-59; Scene::SetTime's bouncing
+ * sphere, spinning cube and swinging quad light): new records for primitives [first, first + count),
+ * triangles included, under the contract of rt_scene_update_triangles -- afterwards the scene is bit for
+ * bit a fresh rt_scene_create of the new description over the same tree topology (leaf-slot records,
+ * shading records, the cubes' and quads' side table, every node box, the sticky boxes), it blocks the
+ * same way, and the next frame is rendered with reset = 1.  prims_dev: DEVICE rt_prim[count];
+ * transforms_dev: DEVICE float[16 * count], one mat4 per record as rt_scene_desc.transforms (read for
+ * RT_CUBE and RT_QUAD only), or NULL = identity for all.  A record's type and material must be the
+ * scene's for that id.  If the range holds primitive 0, the light the renderers sample moves with it.
+ *   RT_ERR_INVALID      null pointer, range outside the primitives, a record whose type or material
+ *                       differs from the scene's, a NaN / infinite field that its kind reads, transform
+ *                       (where one is read) or resulting box -- checked in a pass of its own before
+ *                       anything is written: the scene is untouched;
+ *   RT_ERR_UNSUPPORTED  an SBVH scene, or one built with RT_PT_QUADS=1.
+ * count == 0 is RT_OK and does nothing. */
+int rt_scene_update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev,
+                          const float *transforms_dev, void *stream);
+/* the same with records and transforms (may be NULL) in host memory */
+int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims, const float *transforms);
+/* Whole meshes moved rigidly (or by any affine mat4), many in one call: triangle primitives
+ * [first, first + count) of each range take the world vertices TransformPosition(rest, M) -- the one
+ * operation Scene::LoadModel places a mesh with (template/scene.h:185-191), exactly as
+ * rt_mesh_to_prims computes it -- and everything after that is rt_scene_update_triangles: one finite
+ * check over the transformed vertices, one update launch, one refit.  ranges: HOST, in any order;
+ * rest_dev: DEVICE object-space A, B, C, 9 floats per triangle, the ranges' triangles back to back in the
+ * order of `ranges`.
+ *   RT_ERR_INVALID      null pointer, a range outside the primitives or over a non-triangle, ranges that
+ *                       overlap (checked on the host), or a transformed vertex that is NaN or infinite --
+ *                       the scene is untouched;
+ *   RT_ERR_UNSUPPORTED  as above.
+ * Ranges of count 0 are skipped; no range at all is RT_OK and does nothing. */
+typedef struct { uint32_t first, count; float M[16]; } rt_tri_xform;
+int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
+                                 void *stream);
 
 /* Batched Scene::IntersectBVH (template/scene.h:285-320): rays_dev[n] -> hits_dev[n]. */
 int rt_intersect(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, uint32_t n, void *stream);

@@ -12,6 +12,10 @@
 //   Tmpl8::Scene::IntersectBVH template/scene.h:285   -> rt_intersect_host (batch of 1 or n)
 //   Tmpl8::Scene::IsOccluded   template/scene.h:452   -> rt_occluded_host
 //   Tmpl8::Scene::IntersectBVHPacket template/scene.h:322 -> rt_intersect_packets_host
+//   Tmpl8::Scene::UpdatePrimitives   Primitive::UpdateTransform (Primitive.h:56-59) / Scene::SetTime
+//                              (template/scene.h:213-224)  -> rt_scene_update_prims_host
+//   Tmpl8::Scene::TransformTriangles Scene::LoadModel's placement (template/scene.h:185-191), again
+//                              and on the device          -> rt_scene_transform_triangles
 //   Tmpl8::Camera              camera.h:28-52         -> rt_camera_default
 //   Tmpl8::Renderer::Init      renderer.cpp:6-12      -> rt_renderer_create (screen size)
 //   Tmpl8::Renderer::Tick      renderer.cpp:200-309   -> rt_render_frame_host into screen->pixels
@@ -204,6 +208,9 @@ class Scene {   // template/scene.h:37
         rt_check(rt_scene_create_recipe(recipe, mesh_dir, device, &h_));
     }
     explicit Scene(const rt_scene_desc &desc) { rt_check(rt_scene_create(&desc, &h_)); }
+    // adopt a handle made through the C-ABI (destroyed with this object); a null handle stays null and
+    // every call on it reports the library's RT_ERR_INVALID
+    explicit Scene(rt_scene *adopted) : h_(adopted) {}
     Scene(const Scene &) = delete;
     Scene &operator=(const Scene &) = delete;
     ~Scene() { rt_scene_destroy(h_); }
@@ -263,11 +270,30 @@ class Scene {   // template/scene.h:37
     void UpdateTrianglesDevice(uint32_t first, const float *verts_dev, uint32_t count, void *stream = nullptr) {
         rt_check(rt_scene_update_triangles(handle(), first, count, verts_dev, stream));
     }
+    // Primitive::UpdateTransform (Primitive.h:56-59) and the rest of Scene::SetTime (template/scene.h:213-224:
+    // the bouncing sphere, the spinning cube, the swinging quad light): new rt_prim records (host memory)
+    // for primitives [first, first + count) of any kind, types and materials unchanged, with one mat4 per
+    // record (16 floats, read for cubes and quads; nullptr = identity) -- in place, then a BVH refit.
+    // A host's SetTime(t) builds the moved records and matrices and calls this once per frame.
+    void UpdatePrimitives(uint32_t first, const rt_prim *prims, const float *transforms, uint32_t count) {
+        rt_check(rt_scene_update_prims_host(handle(), first, count, prims, transforms));
+    }
+    // the same with records and transforms already in device memory, on a hipStream_t
+    void UpdatePrimitivesDevice(uint32_t first, const rt_prim *prims_dev, const float *transforms_dev, uint32_t count,
+                                void *stream = nullptr) {
+        rt_check(rt_scene_update_prims(handle(), first, count, prims_dev, transforms_dev, stream));
+    }
+    // whole meshes moved by matrix as Scene::LoadModel places them (TransformPosition per vertex,
+    // template/scene.h:185-191): every range's triangles from their object-space vertices in device
+    // memory (9 floats per triangle, the ranges back to back), one call and one refit for all of them
+    void TransformTriangles(const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev, void *stream = nullptr) {
+        rt_check(rt_scene_transform_triangles(handle(), ranges, num_ranges, rest_dev, stream));
+    }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
     rt_scene *handle() {
-        if (!h_) create();
+        if (!h_ && !recipe_.empty()) create();   // an adopted null handle has no recipe to create from
         return h_;
     }
 
