@@ -40,15 +40,6 @@
 // ====================================================================== host side
 using namespace rt;
 
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorNoBinaryForGpu || e_ == hipErrorInvalidDeviceFunction    \
-                            ? RT_ERR_NO_DEVICE : RT_ERR_HIP,                                   \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
-    } while (0)
-
 struct rt_scene {
     int device = 0;
     SceneView view{};
@@ -110,19 +101,7 @@ struct rt_scene {
     void *d_scratch = nullptr;  // staging for the host-pointer batched calls
     size_t scratch_bytes = 0;
     hipStream_t stream = nullptr;
-    // in-place triangle updates (rt_scene_update_triangles).  Kept from creation: per primitive its
-    // type | sticky << 7 (mark_sticky) and its box (prim_geometry; 6 floats) -- what a refit needs of
-    // the primitives that do not move.  The plan and its device arrays are built by the first update.
-    std::vector<uint8_t> pinfo;
-    std::vector<float> pbox;
-    double sliver_lim = 0.0;        // mark_sticky's sine limit at creation (RT_WALK_STICKY)
-    bool boxes_finite = true;       // every primitive box was finite at creation
-    bool refit_ready = false;
-    RefitPlan plan;
-    void *d_slot_of = nullptr, *d_slot_box = nullptr, *d_list = nullptr, *d_lvl = nullptr, *d_grp = nullptr, *d_flag = nullptr;
-    bool bvh_stale = false;         // the device boxes are newer than bvh.nodes (rt_scene_copy_bvh downloads them)
-    void *d_ranges = nullptr;       // rt_scene_transform_triangles' range table (first, prefix counts, matrices)
-    size_t ranges_bytes = 0;
+    RefitState refit;           // in-place updates (rt_refit.h)
 };
 
 // renderer streams: up to 8 -- frames in flight of overlapped primary+shadow frames (timed
@@ -252,19 +231,12 @@ void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads,
-                    s->d_slot_of, s->d_slot_box, s->d_list, s->d_lvl, s->d_grp, s->d_flag, s->d_ranges};
+    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    free_refit(s->refit);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
-}
-
-template <typename T>
-int upload(void **dst, const std::vector<T> &src) {
-    HIP_TRY(hipMalloc(dst, std::max<size_t>(sizeof(T) * src.size(), 16)));
-    if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
-    return RT_OK;
 }
 
 int ensure_device(int device) {
@@ -371,9 +343,9 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     s->has_cubes = p.has_cubes;
     s->nested = p.nested;
     s->walk_fits = p.walk_fits;
-    s->boxes_finite = p.boxes_finite;
+    s->refit.boxes_finite = p.boxes_finite;
     s->quads = s->quad_lanes = p.has_quads;
-    s->sliver_lim = o.sliver_lim;
+    s->refit.sliver_lim = o.sliver_lim;
     rc = upload(&s->d_nodes, p.nodes);
     if (rc == RT_OK) rc = upload(&s->d_prims, p.prims);
     if (rc == RT_OK) rc = upload(&s->d_shade, p.shade);
@@ -386,8 +358,8 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
         rc = fail(RT_ERR_HIP, "hipStreamCreate failed");
     if (rc != RT_OK) { free_scene(s); return rc; }
     s->bvh = std::move(p.bvh);
-    s->pinfo = std::move(p.pinfo);
-    s->pbox = std::move(p.pbox);
+    s->refit.pinfo = std::move(p.pinfo);
+    s->refit.pbox = std::move(p.pbox);
 
     SceneView &v = s->view;
     v = p.view;
@@ -1483,7 +1455,7 @@ int rt_scene_set_camera_walk(rt_scene *s, int walk) {
 int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
     if (!cs || !nodes || !indices) return fail(RT_ERR_INVALID, "null argument");
     rt_scene *s = const_cast<rt_scene *>(cs);
-    if (s->bvh_stale) {   // boxes refitted on the device since the last copy (updates block, so they are settled)
+    if (s->refit.bvh_stale) {   // boxes refitted on the device since the last copy (updates block, so they are settled)
         HIP_TRY(hipSetDevice(s->device));
         std::vector<float4> dn(2 * (size_t)s->bvh.nodes_used);
         HIP_TRY(hipMemcpy(dn.data(), s->d_nodes, sizeof(float4) * dn.size(), hipMemcpyDeviceToHost));
@@ -1494,86 +1466,15 @@ int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
             nd.mn[0] = mn.x; nd.mn[1] = mn.y; nd.mn[2] = mn.z;
             nd.mx[0] = mx.x; nd.mx[1] = mx.y; nd.mx[2] = mx.z;
         }
-        s->bvh_stale = false;
+        s->refit.bvh_stale = false;
     }
     std::memcpy(nodes, s->bvh.nodes.data(), sizeof(Node) * s->bvh.nodes_used);
     std::memcpy(indices, s->bvh.indices.data(), sizeof(uint32_t) * s->bvh.indices.size());
     return RT_OK;
 }
 
-// the refit plan and its device arrays, on the first update of a scene
-static int ensure_refit(rt_scene *s) {
-    if (s->refit_ready) return RT_OK;
-    const uint32_t n = s->num_prims;
-    if (!build_refit_plan(s->bvh, n, s->plan)) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
-    std::vector<float4> box(2 * (size_t)n);
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint32_t id = s->bvh.indices[k];
-        const float *b = &s->pbox[6 * (size_t)id];
-        slot_box(mk(b[0], b[1], b[2]), mk(b[3], b[4], b[5]), (s->pinfo[id] & 0x80) != 0, &box[2 * (size_t)k]);
-    }
-    int rc = upload(&s->d_slot_of, s->plan.slot_of);
-    if (rc == RT_OK) rc = upload(&s->d_slot_box, box);
-    if (rc == RT_OK) rc = upload(&s->d_list, s->plan.list);
-    if (rc == RT_OK) rc = upload(&s->d_lvl, s->plan.lvl);
-    if (rc == RT_OK) rc = upload(&s->d_grp, s->plan.grp);
-    if (rc == RT_OK && !s->d_flag && hipMalloc(&s->d_flag, 16) != hipSuccess) rc = fail(RT_ERR_HIP, "hipMalloc failed");
-    if (rc != RT_OK) {
-        for (void **p : {&s->d_slot_of, &s->d_slot_box, &s->d_list, &s->d_lvl, &s->d_grp}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
-        return rc;
-    }
-    std::vector<float>().swap(s->pbox);   // the boxes and the schedule live on the device from here on
-    for (std::vector<uint32_t> *v : {&s->plan.slot_of, &s->plan.list, &s->plan.lvl, &s->plan.grp}) std::vector<uint32_t>().swap(*v);
-    s->refit_ready = true;
-    return RT_OK;
-}
-
-static RefitArgs refit_args(const rt_scene *s) {
-    RefitArgs A{};
-    A.nodes = (float4 *)s->d_nodes; A.prims = (float4 *)s->d_prims; A.shade = (float4 *)s->d_shade;
-    A.slot_box = (float4 *)s->d_slot_box;
-    A.slot_of = (const uint32_t *)s->d_slot_of; A.list = (const uint32_t *)s->d_list;
-    A.lvl = (const uint32_t *)s->d_lvl; A.grp = (const uint32_t *)s->d_grp;
-    A.margin = s->view.walk_margin;
-    A.sliver_lim = s->sliver_lim;
-    return A;
-}
-
-// after an update kernel on `st`: the refit, then the scene's flags from the new root box
-static int refit_and_settle(rt_scene *s, const RefitArgs &A, hipStream_t st) {
-    launch_refit(A, s->plan.ntreelets, s->plan.has_top, st);
-    HIP_TRY(hipGetLastError());
-    s->bvh_stale = true;
-    float4 root[2];
-    HIP_TRY(hipMemcpyAsync(root, s->d_nodes, sizeof(root), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const float rb[6] = {root[0].x, root[0].y, root[0].z, root[0].w, root[1].x, root[1].y};
-    bool finite = s->boxes_finite;
-    for (float f : rb) finite = finite && std::isfinite(f);
-    s->view.bounds_finite = finite ? 1 : 0;
-    if (finite) s->nested = true;   // every box is now the union of finite boxes below it
-    return RT_OK;
-}
-
-static int update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st) {
-    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
-    int rc = ensure_refit(s);
-    if (rc != RT_OK) return rc;
-    // the finite check is a pass of its own, read back before anything is written
-    uint32_t bad = 0;
-    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
-    launch_check_finite(verts_dev, 9u * count, (uint32_t *)s->d_flag, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: a vertex is NaN or infinite");
-    const RefitArgs A = refit_args(s);
-    launch_update_tris(A, first, count, verts_dev, st);
-    return refit_and_settle(s, A, st);
-}
+// ---- in-place updates.  The entry points check their arguments; the device work -- check, write,
+// refit, one path for all of them -- is update() of rt_refit.hip.
 
 // an in-place update needs a plain tree (every primitive in one leaf) with the binary node array alone
 static int refit_supported(const rt_scene *s, const char *who) {
@@ -1582,84 +1483,40 @@ static int refit_supported(const rt_scene *s, const char *who) {
     if (s->quads) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": scene built with two-level node records (RT_PT_QUADS=1)");
     return RT_OK;
 }
-
-static int update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
-                        hipStream_t st) {
-    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
-    int rc = ensure_refit(s);
-    if (rc != RT_OK) return rc;
-    // validation is a pass of its own, its flag read back before anything is written; the light's
-    // record and matrix come back with it
-    uint32_t bad = 0;
-    rt_prim light{};
-    float lightT[16];
-    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
-    launch_check_prims((const float4 *)s->d_shade, first, count, prims_dev, transforms_dev, (uint32_t *)s->d_flag, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
-    if (first == 0) {
-        HIP_TRY(hipMemcpyAsync(&light, prims_dev, sizeof(light), hipMemcpyDeviceToHost, st));
-        if (transforms_dev) HIP_TRY(hipMemcpyAsync(lightT, transforms_dev, sizeof(lightT), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad)
-        return fail(RT_ERR_INVALID, "rt_scene_update_prims: a record's type or material is not the scene's, or a field, "
-                                    "transform or box is NaN or infinite");
-    const RefitArgs A = refit_args(s);
-    launch_update_prims(A, (float4 *)s->d_xprims, first, count, prims_dev, transforms_dev, st);
-    // SceneView travels by value with every launch (renderers and the multi-GPU frames read
-    // s->view per frame), so the light's fields change here and nowhere else
-    if (first == 0) fill_light(light, transforms_dev ? lightT : nullptr, s->view);
-    return refit_and_settle(s, A, st);
+static int require_triangles(const rt_scene *s, uint32_t first, uint32_t count, const char *who) {
+    for (uint32_t id = first; id < first + count; ++id)
+        if ((s->refit.pinfo[id] & 0x7f) != RT_TRIANGLE)
+            return fail(RT_ERR_INVALID, std::string(who) + ": primitive " + std::to_string(id) + " is not a triangle");
+    return RT_OK;
 }
-
-static int transform_triangles(rt_scene *s, const std::vector<uint32_t> &tab, uint32_t nr, uint32_t total,
-                               const float *rest_dev, hipStream_t st) {
-    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene; the range table of an earlier call
-    int rc = ensure_refit(s);
+static SceneRecords records_of(const rt_scene *s) {
+    return SceneRecords{&s->bvh, s->num_prims, s->d_nodes, s->d_prims, s->d_shade, s->d_xprims, s->view.walk_margin};
+}
+// after an update: the scene's flags from the new root box
+static int settle(rt_scene *s, int rc, bool finite) {
     if (rc != RT_OK) return rc;
-    const size_t need = sizeof(uint32_t) * tab.size();
-    if (need > s->ranges_bytes) {
-        if (s->d_ranges) HIP_TRY(hipFree(s->d_ranges));
-        s->d_ranges = nullptr;
-        s->ranges_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_ranges, need));
-        s->ranges_bytes = need;
-    }
-    HIP_TRY(hipMemcpyAsync(s->d_ranges, tab.data(), need, hipMemcpyHostToDevice, st));
-    XformRanges R{};
-    R.first = (const uint32_t *)s->d_ranges;
-    R.pre = R.first + nr;
-    R.M = (const float *)(R.pre + nr + 1);
-    R.nr = nr;
-    uint32_t bad = 0;
-    HIP_TRY(hipMemsetAsync(s->d_flag, 0, 4, st));
-    launch_check_xform(R, total, rest_dev, (uint32_t *)s->d_flag, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&bad, s->d_flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));   // the table has left the host vector too
-    if (bad) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: a transformed vertex is NaN or infinite");
-    const RefitArgs A = refit_args(s);
-    launch_xform_tris(A, R, total, rest_dev, st);
-    return refit_and_settle(s, A, st);
+    s->view.bounds_finite = finite ? 1 : 0;
+    if (finite) s->nested = true;   // every box is now the union of finite boxes below it
+    return RT_OK;
 }
 
 int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream) {
+    const char *who = "rt_scene_update_triangles";
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null scene");
     if (count == 0) return RT_OK;
     if (!verts_dev) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null vertices");
-    if (s->bvh.indices.size() != s->num_prims)
-        return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles: an SBVH scene (leaves share primitives) cannot be refitted");
-    if (s->quads) return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles: scene built with two-level node records (RT_PT_QUADS=1)");
+    int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
     if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: range outside the primitives");
-    for (uint32_t id = first; id < first + count; ++id)
-        if ((s->pinfo[id] & 0x7f) != RT_TRIANGLE)
-            return fail(RT_ERR_INVALID, "rt_scene_update_triangles: primitive " + std::to_string(id) + " is not a triangle");
+    if ((rc = require_triangles(s, first, count, who)) != RT_OK) return rc;
     HIP_TRY(hipSetDevice(s->device));
     try {
-        return update_triangles(s, first, count, verts_dev, (hipStream_t)stream);
+        bool finite = false;
+        rc = update(s->refit, records_of(s), TriVerts{first, verts_dev}, count, (hipStream_t)stream,
+                    "rt_scene_update_triangles: a vertex is NaN or infinite", nullptr, 0, &finite);
+        return settle(s, rc, finite);
     } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string("rt_scene_update_triangles: ") + e.what());
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
 }
 
@@ -1671,40 +1528,39 @@ int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, 
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
     const size_t need = 36 * (size_t)count;
-    if (need > s->scratch_bytes) {
-        if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
-        s->d_scratch = nullptr;
-        s->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch, need));
-        s->scratch_bytes = need;
-    }
+    int rc = grow(&s->d_scratch, &s->scratch_bytes, need);
+    if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(s->d_scratch, verts, need, hipMemcpyHostToDevice, s->stream));
     return rt_scene_update_triangles(s, first, count, (const float *)s->d_scratch, s->stream);
 }
 
-static int ensure_scratch(rt_scene *s, size_t need) {
-    if (need <= s->scratch_bytes) return RT_OK;
-    if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
-    s->d_scratch = nullptr;
-    s->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&s->d_scratch, need));
-    s->scratch_bytes = need;
-    return RT_OK;
-}
-
 int rt_scene_update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
                           void *stream) {
+    const char *who = "rt_scene_update_prims";
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null scene");
     if (count == 0) return RT_OK;
     if (!prims_dev) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null records");
-    int rc = refit_supported(s, "rt_scene_update_prims");
+    int rc = refit_supported(s, who);
     if (rc != RT_OK) return rc;
     if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims: range outside the primitives");
     HIP_TRY(hipSetDevice(s->device));
     try {
-        return update_prims(s, first, count, prims_dev, transforms_dev, (hipStream_t)stream);
+        // the light's record and matrix come back with the check's flag
+        rt_prim light{};
+        float lightT[16];
+        bool finite = false;
+        const UpdateCopy back[2] = {{&light, prims_dev, sizeof(light), hipMemcpyDeviceToHost},
+                                    {lightT, transforms_dev, sizeof(lightT), hipMemcpyDeviceToHost}};
+        rc = update(s->refit, records_of(s), PrimRecs{first, prims_dev, transforms_dev}, count, (hipStream_t)stream,
+                    "rt_scene_update_prims: a record's type or material is not the scene's, or a field, "
+                    "transform or box is NaN or infinite",
+                    back, first != 0 ? 0 : transforms_dev ? 2 : 1, &finite);
+        // SceneView travels by value with every launch (renderers and the multi-GPU frames read
+        // s->view per frame), so the light's fields change here and nowhere else
+        if (rc == RT_OK && first == 0) fill_light(light, transforms_dev ? lightT : nullptr, s->view);
+        return settle(s, rc, finite);
     } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string("rt_scene_update_prims: ") + e.what());
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
 }
 
@@ -1716,7 +1572,7 @@ int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, cons
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
     const size_t pbytes = (sizeof(rt_prim) * (size_t)count + 15u) & ~(size_t)15u, tbytes = transforms ? 64 * (size_t)count : 0;
-    int rc = ensure_scratch(s, pbytes + tbytes);
+    int rc = grow(&s->d_scratch, &s->scratch_bytes, pbytes + tbytes);
     if (rc != RT_OK) return rc;
     char *base = (char *)s->d_scratch;
     HIP_TRY(hipMemcpyAsync(base, prims, sizeof(rt_prim) * (size_t)count, hipMemcpyHostToDevice, s->stream));
@@ -1727,10 +1583,11 @@ int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, cons
 
 int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
                                  void *stream) {
+    const char *who = "rt_scene_transform_triangles";
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null scene");
     if (num_ranges == 0) return RT_OK;
     if (!ranges) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null ranges");
-    int rc = refit_supported(s, "rt_scene_transform_triangles");
+    int rc = refit_supported(s, who);
     if (rc != RT_OK) return rc;
     try {
         // the table: first[nr], prefix counts[nr + 1], matrices[16 nr] -- empty ranges dropped
@@ -1743,9 +1600,7 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
                 return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: range " + std::to_string(r) + " outside the primitives");
             if ((uint64_t)pre.back() + x.count > 0xffffffffull / 9u)
                 return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: too many triangles");
-            for (uint32_t id = x.first; id < x.first + x.count; ++id)
-                if ((s->pinfo[id] & 0x7f) != RT_TRIANGLE)
-                    return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: primitive " + std::to_string(id) + " is not a triangle");
+            if ((rc = require_triangles(s, x.first, x.count, who)) != RT_OK) return rc;
             firsts.push_back(x.first);
             pre.push_back(pre.back() + x.count);
             const uint32_t *m = reinterpret_cast<const uint32_t *>(x.M);
@@ -1758,14 +1613,17 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
             if (spans[k - 1].first + spans[k - 1].second > spans[k].first)
                 return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: ranges overlap");
         if (!rest_dev) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null rest vertices");
-        const uint32_t nr = (uint32_t)firsts.size(), total = pre.back();
+        const uint32_t nr = (uint32_t)firsts.size();
         std::vector<uint32_t> tab(firsts);
         tab.insert(tab.end(), pre.begin(), pre.end());
         tab.insert(tab.end(), mats.begin(), mats.end());
         HIP_TRY(hipSetDevice(s->device));
-        return transform_triangles(s, tab, nr, total, rest_dev, (hipStream_t)stream);
+        bool finite = false;
+        rc = update_xform(s->refit, records_of(s), tab, nr, rest_dev, (hipStream_t)stream,
+                          "rt_scene_transform_triangles: a transformed vertex is NaN or infinite", &finite);
+        return settle(s, rc, finite);
     } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string("rt_scene_transform_triangles: ") + e.what());
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
 }
 
@@ -1830,13 +1688,7 @@ int rt_trace_host(rt_scene *s, int mode, const rt_ray *rays, uint32_t *seeds, co
     const size_t o_seed = up(sizeof(rt_ray) * (size_t)n), o_flag = o_seed + up(4 * (size_t)n),
                  o_rad = o_flag + up((size_t)n), o_hit = o_rad + up(12 * (size_t)n),
                  o_cnt = o_hit + up(sizeof(rt_hit) * (size_t)n), need = o_cnt + 256;
-    if (need > s->scratch_bytes) {
-        if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
-        s->d_scratch = nullptr;
-        s->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch, need));
-        s->scratch_bytes = need;
-    }
+    if (int rc = grow(&s->d_scratch, &s->scratch_bytes, need)) return rc;
     char *b = (char *)s->d_scratch;
     HIP_TRY(hipMemcpyAsync(b, rays, sizeof(rt_ray) * n, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(b + o_seed, seeds, 4 * (size_t)n, hipMemcpyHostToDevice, s->stream));
@@ -1860,13 +1712,7 @@ static int staged_call(rt_scene *s, const rt_ray *rays, void *out, size_t out_el
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
     size_t need = (size_t)n * (sizeof(rt_ray) + out_elem) + 256;
-    if (need > s->scratch_bytes) {
-        if (s->d_scratch) HIP_TRY(hipFree(s->d_scratch));
-        s->d_scratch = nullptr;
-        s->scratch_bytes = 0;
-        HIP_TRY(hipMalloc(&s->d_scratch, need));
-        s->scratch_bytes = need;
-    }
+    if (int rc = grow(&s->d_scratch, &s->scratch_bytes, need)) return rc;
     rt_ray *d_rays = (rt_ray *)s->d_scratch;
     char *d_out = (char *)s->d_scratch + (((size_t)n * sizeof(rt_ray) + 255) & ~(size_t)255);
     HIP_TRY(hipMemcpyAsync(d_rays, rays, sizeof(rt_ray) * n, hipMemcpyHostToDevice, s->stream));

@@ -1,7 +1,7 @@
 // rt_records.h -- the encoders of the device scene records whose bits the frames depend on.
 //
 // One definition each, compiled from the same text for the host (rt_scene_pack.cpp at scene
-// creation, rt_host.cpp) and for gfx950 (the refit kernels of rt_refit.hip), under the same
+// creation, rt_host.cpp) and for gfx950 (the update kernels of rt_refit.hip, through rt_update.h), under the same
 // -ffp-contract=off: a scene updated in place equals a freshly created one bit for bit
 // because both run these functions.  Built on rt_math.h and the HIP vector types (rt_dev_types.h
 // for the T_* tags); no std:: algorithm, so a plain host program compiles it too

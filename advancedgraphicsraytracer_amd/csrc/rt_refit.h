@@ -1,13 +1,25 @@
-// rt_refit.h -- in-place updates: the refit plan of a scene's tree and the launchers of the kernels
-// in rt_refit.hip (rt_scene_update_triangles, rt_scene_update_prims, rt_scene_transform_triangles;
-// rt_device.hip).
+// rt_refit.h -- in-place updates: the refit plan of a scene's tree (built in rt_scene_pack.cpp),
+// the update state a scene keeps, and the one host path of rt_refit.hip that every update entry
+// point of rt_device.hip takes (rt_scene_update_triangles, rt_scene_update_prims,
+// rt_scene_transform_triangles).  The per-lane text is in rt_update.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
 #include "rt_internal.h"
+#include "rt_update.h"
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(e_ == hipErrorNoBinaryForGpu || e_ == hipErrorInvalidDeviceFunction    \
+                            ? RT_ERR_NO_DEVICE : RT_ERR_HIP,                                   \
+                        std::string(#expr) + ": " + hipGetErrorString(e_));                   \
+    } while (0)
 
 namespace rt {
 
@@ -31,35 +43,72 @@ struct RefitPlan {
 };
 // false when the tree is not a plain one (a primitive in no leaf or in two)
 bool build_refit_plan(const Bvh &b, uint32_t num_prims, RefitPlan &out);
+// the slot boxes a refit starts from: per leaf slot k the box and sticky flag (pbox, pinfo of
+// ScenePack) of primitive indices[k]
+void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std::vector<float> &pbox, std::vector<float4> &out);
 
-struct RefitArgs {
-    float4 *nodes, *prims, *shade;   // the scene's device records (SceneView)
-    float4 *slot_box;                // 2 float4 per leaf slot: (box min, sticky flag), (box max, 0)
-    const uint32_t *slot_of, *list, *lvl, *grp;
-    float margin;                    // SceneView::walk_margin
-    double sliver_lim;               // mark_sticky's sine limit
+// What a scene keeps for its updates and for nothing else.  Kept from creation: per primitive its
+// type | sticky << 7 (mark_sticky) and its box (prim_geometry; 6 floats) -- what a refit needs of
+// the primitives that do not move.  The plan and its device arrays are built by the first update;
+// the boxes and the schedule live on the device from there on.
+struct RefitState {
+    std::vector<uint8_t> pinfo;
+    std::vector<float> pbox;
+    double sliver_lim = 0.0;        // mark_sticky's sine limit at creation (RT_WALK_STICKY)
+    bool boxes_finite = true;       // every primitive box was finite at creation
+    bool refit_ready = false;
+    RefitPlan plan;
+    void *d_slot_of = nullptr, *d_slot_box = nullptr, *d_list = nullptr, *d_lvl = nullptr, *d_grp = nullptr, *d_flag = nullptr;
+    bool bvh_stale = false;         // the device boxes are newer than the host tree (rt_scene_copy_bvh downloads them)
+    void *d_ranges = nullptr;       // rt_scene_transform_triangles' range table (first, prefix counts, matrices)
+    size_t ranges_bytes = 0;
 };
-// *flag_dev = 1 if any of the n floats is NaN or infinite (untouched otherwise)
-void launch_check_finite(const float *verts_dev, uint32_t n, uint32_t *flag_dev, hipStream_t st);
-void launch_update_tris(const RefitArgs &A, uint32_t first, uint32_t count, const float *verts_dev, hipStream_t st);
-// rt_scene_update_prims: records of any kind for primitives [first, first + count), one transform
-// (16 floats) per record or none.  The check sets *flag_dev = 1 on a type or material that is not
-// the scene's, a NaN / infinite field, transform or box; the update also takes the side table.
-void launch_check_prims(const float4 *shade, uint32_t first, uint32_t count, const rt_prim *prims_dev,
-                        const float *transforms_dev, uint32_t *flag_dev, hipStream_t st);
-void launch_update_prims(const RefitArgs &A, float4 *xprims, uint32_t first, uint32_t count, const rt_prim *prims_dev,
-                         const float *transforms_dev, hipStream_t st);
-// rt_scene_transform_triangles' range table in device memory: range r moves triangles
-// [first[r], first[r] + pre[r + 1] - pre[r]) by M[16 r ..]; pre[nr] = all triangles of the call
-struct XformRanges {
-    const uint32_t *first, *pre;
-    const float *M;
-    uint32_t nr;
+void free_refit(RefitState &R);
+
+// the scene's side of an update: its tree and its device records
+struct SceneRecords {
+    const Bvh *bvh;
+    uint32_t num_prims;
+    void *nodes, *prims, *shade, *xprims;
+    float margin;   // SceneView::walk_margin
 };
-// *flag_dev = 1 if a transformed vertex is NaN or infinite; then the triangles' records from them
-void launch_check_xform(const XformRanges &R, uint32_t total, const float *rest_dev, uint32_t *flag_dev, hipStream_t st);
-void launch_xform_tris(const RefitArgs &A, const XformRanges &R, uint32_t total, const float *rest_dev, hipStream_t st);
-// the treelets, then (a second launch) the nodes above the cut
-void launch_refit(const RefitArgs &A, uint32_t ntreelets, bool has_top, hipStream_t st);
+
+// a device buffer of at least `need` bytes (the old one is freed, its contents are not kept)
+inline int grow(void **buf, size_t *have, size_t need) {
+    if (need <= *have) return RT_OK;
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    HIP_TRY(hipMalloc(buf, need));
+    *have = need;
+    return RT_OK;
+}
+template <typename T>
+int upload(void **dst, const std::vector<T> &src) {
+    HIP_TRY(hipMalloc(dst, std::max<size_t>(sizeof(T) * src.size(), 16)));
+    if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// a copy that rides along with an update, enqueued on its stream before the one synchronise that
+// follows the check
+struct UpdateCopy {
+    void *dst;
+    const void *src;
+    size_t bytes;
+    hipMemcpyKind kind;
+};
+// One in-place update of n lanes of `src` (TriVerts, TriXform or PrimRecs over device memory) on
+// `st`: waits for the frames still reading the scene, builds the plan on the scene's first update,
+// runs the check and reads its flag back -- a refusal (RT_ERR_INVALID, `refusal`) has written
+// nothing --, then the write, the refit of every treelet and of the nodes above the cut, and the
+// new root box.  Blocks.  *finite = every box of the tree is finite now.
+template <class Src>
+int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *refusal,
+           const UpdateCopy *copies, int ncopies, bool *finite);
+// the same for ranges of triangles moved by one matrix each; tab = first[nr], prefix counts[nr + 1],
+// matrices[16 nr], uploaded to the scene's range table
+int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
+                 hipStream_t st, const char *refusal, bool *finite);
 
 }  // namespace rt

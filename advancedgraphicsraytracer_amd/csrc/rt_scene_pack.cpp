@@ -10,6 +10,7 @@
 
 #include "rt_internal.h"
 #include "rt_records.h"
+#include "rt_refit.h"
 
 namespace rt {
 namespace {
@@ -393,6 +394,66 @@ int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &s) {
     v.stack_entries = s.stack_depth;
     tree_flags(s);
     return RT_OK;
+}
+
+// ---------------------------------------------------------------- what an in-place update starts from (rt_refit.h)
+
+bool build_refit_plan(const Bvh &b, uint32_t num_prims, RefitPlan &out) {
+    const uint32_t used = b.nodes_used;
+    const Node *N = b.nodes.data();
+    if (b.indices.size() != num_prims) return false;
+    out = RefitPlan();
+    out.slot_of.assign(num_prims, ~0u);
+    for (uint32_t k = 0; k < num_prims; ++k) {
+        const uint32_t id = b.indices[k];
+        if (id >= num_prims || out.slot_of[id] != ~0u) return false;
+        out.slot_of[id] = k;
+    }
+    // pre-order from the root; sizes and heights in reverse
+    TreeWalk w;
+    if (walk_tree(N, used, num_prims, w) != kTreeOk) return false;
+    const std::vector<uint32_t> &order = w.order;
+    std::vector<uint32_t> size(used, 0), height(used, 0);
+    for (size_t i = order.size(); i-- > 0;) {
+        const uint32_t k = order[i];
+        size[k] = 1;
+        if (N[k].count > 0) continue;
+        const uint32_t l = N[k].leftFirst;
+        size[k] += size[l] + size[l + 1];
+        height[k] = 1 + std::max(height[l], height[l + 1]);
+    }
+    auto by_height = [&](uint32_t x, uint32_t y) { return height[x] < height[y]; };
+    auto emit = [&](std::vector<uint32_t> &nodes) {   // one group: its nodes by height, its level boundaries
+        std::stable_sort(nodes.begin(), nodes.end(), by_height);
+        out.grp.push_back((uint32_t)out.lvl.size());
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            if (i == 0 || height[nodes[i]] != height[nodes[i - 1]]) out.lvl.push_back((uint32_t)out.list.size());
+            out.list.push_back(nodes[i]);
+        }
+        out.lvl.push_back((uint32_t)out.list.size());
+    };
+    std::vector<uint32_t> top, sub;
+    for (size_t i = 0; i < order.size(); ++i) {   // pre-order: a treelet's size[k] nodes start at its root
+        const uint32_t k = order[i];
+        if (size[k] > kTreeletNodes) { top.push_back(k); continue; }
+        if (k != 0 && size[w.parent[k]] <= kTreeletNodes) continue;   // inside a treelet
+        sub.assign(order.begin() + i, order.begin() + i + size[k]);
+        emit(sub);
+        ++out.ntreelets;
+    }
+    out.has_top = !top.empty();
+    emit(top);
+    out.grp.push_back((uint32_t)out.lvl.size());
+    return true;
+}
+
+void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std::vector<float> &pbox, std::vector<float4> &out) {
+    out.resize(2 * b.indices.size());
+    for (size_t k = 0; k < b.indices.size(); ++k) {
+        const uint32_t id = b.indices[k];
+        const float *x = &pbox[6 * (size_t)id];
+        slot_box(mk(x[0], x[1], x[2]), mk(x[3], x[4], x[5]), (pinfo[id] & 0x80) != 0, &out[2 * k]);
+    }
 }
 
 }  // namespace rt

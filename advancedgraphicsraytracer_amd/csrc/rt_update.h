@@ -1,0 +1,189 @@
+// rt_update.h -- the per-lane text of the in-place updates: what one lane of the
+// check, write and refit kernels of rt_refit.hip does, as plain functions over arrays.
+//
+// One text for gfx950 and for the host, like rt_records.h and under the same -ffp-contract=off:
+// the kernels only supply the lane index and the barrier between heights, so a stand-alone host
+// program runs check -> write -> refit end to end with tid = 0, stride = 1
+// (tests/cpp/update_host.cpp, tests/cpp/prim_records_host.cpp).  No std:: algorithm.
+//
+// A *source* maps lane i of a call to "primitive id + its new geometry":
+//   ok(A, i)     would the write of lane i produce a finite, admissible record?  Writes nothing;
+//   write(A, i)  the leaf-slot record, the shading record, the slot box (and, for a cube or a quad,
+//                the side-table entry) of that primitive.
+#pragma once
+#include "rt_records.h"
+
+namespace rt {
+
+struct RefitArgs {
+    float4 *nodes, *prims, *shade;   // the scene's records (SceneView)
+    float4 *xprims;                  // the side table of cubes and quads
+    float4 *slot_box;                // 2 float4 per leaf slot: (box min, sticky flag), (box max, 0)
+    const uint32_t *slot_of, *list, *lvl, *grp;   // the refit plan (RefitPlan, rt_refit.h)
+    float margin;                    // SceneView::walk_margin
+    double sliver_lim;               // mark_sticky's sine limit
+};
+
+RT_HD bool finite_f(float f) { return (fbits(f) & 0x7f800000u) != 0x7f800000u; }
+RT_HD bool finite_f3(f3 a) { return finite_f(a.x) && finite_f(a.y) && finite_f(a.z); }
+
+// ---- triangles from nine world-space floats
+RT_HD bool tri_ok(const float w[9]) {
+    bool ok = true;
+    for (int k = 0; k < 9; ++k) ok = ok && finite_f(w[k]);
+    return ok;
+}
+// the rt_records.h encoders that scene creation runs, so the records equal those of a fresh
+// rt_scene_create on the new vertices; the material word of the shading record stays
+RT_HD void write_tri(const RefitArgs &A, uint32_t id, const float w[9]) {
+    const uint32_t slot = A.slot_of[id];
+    const f3 N = tri_normal(w);
+    A.shade[2 * (size_t)id] = make_float4(N.x, N.y, N.z, A.shade[2 * (size_t)id].w);
+    tri_record(w, id, A.prims + 3 * (size_t)slot);
+    f3 mn, mx;
+    tri_box(w, mn, mx);
+    slot_box(mn, mx, tri_sliver(w, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
+}
+
+// rt_scene_update_triangles: triangle first + i from the nine floats at verts + 9 i
+struct TriVerts {
+    uint32_t first;
+    const float *verts;
+    RT_HD bool ok(const RefitArgs &, uint32_t i) const { return tri_ok(verts + 9u * (size_t)i); }
+    RT_HD void write(const RefitArgs &A, uint32_t i) const { write_tri(A, first + i, verts + 9u * (size_t)i); }
+};
+
+// rt_scene_transform_triangles' range table: range r moves triangles
+// [first[r], first[r] + pre[r + 1] - pre[r]) by M[16 r ..]; pre[nr] = all triangles of the call
+struct XformRanges {
+    const uint32_t *first, *pre;
+    const float *M;
+    uint32_t nr;
+};
+// Lane i of the back-to-back rest triangles finds its range by binary search over the prefix
+// counts (pre[r] = triangles before range r).
+RT_HD uint32_t range_of(const uint32_t *pre, uint32_t nr, uint32_t i) {
+    uint32_t lo = 0, hi = nr;   // pre[lo] <= i < pre[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pre[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+struct TriXform {
+    XformRanges R;
+    const float *rest;   // object-space vertices, 9 floats per lane
+    // world vertices = TransformPosition(rest, M) per vertex, as Scene::LoadModel places a mesh
+    // (template/scene.h:185-191); returns the triangle's id
+    RT_HD uint32_t world(uint32_t i, float w[9]) const {
+        const uint32_t r = range_of(R.pre, R.nr, i);
+        const float *M = R.M + 16u * (size_t)r;
+        const float *q = rest + 9u * (size_t)i;
+        for (int k = 0; k < 3; ++k) {
+            const f3 v = tpos(M, mk(q[3 * k], q[3 * k + 1], q[3 * k + 2]));
+            w[3 * k] = v.x; w[3 * k + 1] = v.y; w[3 * k + 2] = v.z;
+        }
+        return R.first[r] + (i - R.pre[r]);
+    }
+    RT_HD bool ok(const RefitArgs &, uint32_t i) const {
+        float w[9];
+        world(i, w);
+        return tri_ok(w);
+    }
+    RT_HD void write(const RefitArgs &A, uint32_t i) const {
+        float w[9];
+        const uint32_t id = world(i, w);
+        write_tri(A, id, w);
+    }
+};
+
+// rt_scene_update_prims: record i of any kind for primitive first + i, with transform T + 16 i
+// (T may be null) where its kind reads one -- cubes and quads
+struct PrimRecs {
+    uint32_t first;
+    const rt_prim *prims;
+    const float *T;
+    RT_HD const float *transform(const rt_prim &p, uint32_t i) const {
+        return (T && (p.type == RT_CUBE || p.type == RT_QUAD)) ? T + 16u * (size_t)i : nullptr;
+    }
+    // type and material as the scene holds them (the shading record's words), every field the
+    // kind reads finite, its transform finite where one is read, its box finite
+    RT_HD bool ok(const RefitArgs &A, uint32_t i) const {
+        const uint32_t id = first + i;
+        const rt_prim p = prims[i];
+        if ((uint32_t)p.type != fbits(A.shade[2 * (size_t)id + 1].x) || (uint32_t)p.material != fbits(A.shade[2 * (size_t)id].w))
+            return false;
+        bool ok = true;
+        const int nf = p.type == RT_TRIANGLE ? 9 : p.type == RT_CUBE ? 6 : p.type == RT_QUAD ? 1 : 4;
+        for (int k = 0; k < nf; ++k) ok = ok && finite_f(p.v[k]);
+        const float *Ti = transform(p, i);
+        for (int k = 0; Ti && k < 16; ++k) ok = ok && finite_f(Ti[k]);
+        PrimX x;
+        PrimGeom g;
+        prim_transform(p, Ti, x);
+        prim_geometry(p, x, g);
+        return ok && finite_f3(g.bmin) && finite_f3(g.bmax);
+    }
+    // the leaf-slot record, the shading record (material word kept), a cube's or a quad's
+    // side-table entry (through the index its shading record holds) and the slot box; the sticky
+    // flag is tri_sliver's for a triangle and stays as it is for every other kind (mark_sticky's
+    // depends on the kind alone)
+    RT_HD void write(const RefitArgs &A, uint32_t i) const {
+        const uint32_t id = first + i, slot = A.slot_of[id];
+        const rt_prim p = prims[i];
+        PrimX x;
+        PrimGeom g;
+        prim_transform(p, transform(p, i), x);
+        prim_geometry(p, x, g);
+        const float4 old0 = A.shade[2 * (size_t)id], old1 = A.shade[2 * (size_t)id + 1];
+        const uint32_t xi = fbits(old1.z);
+        float4 s[2];
+        prim_shade(p, x, xi, s);
+        s[0].w = old0.w;
+        A.shade[2 * (size_t)id] = s[0];
+        A.shade[2 * (size_t)id + 1] = s[1];
+        prim_record(p, x, id, xi, A.prims + 3 * (size_t)slot);
+        if (p.type == RT_CUBE || p.type == RT_QUAD) prim_xentry(p, x, A.xprims + 8 * (size_t)xi);
+        const bool sticky = p.type == RT_TRIANGLE ? tri_sliver(p.v, A.sliver_lim) : slot_sticky(A.slot_box[2 * (size_t)slot]);
+        slot_box(g.bmin, g.bmax, sticky, A.slot_box + 2 * (size_t)slot);
+    }
+};
+
+// ---- the refit.  A leaf folds its slots' boxes as Scene::UpdateNodeBounds does
+// (template/scene.h:855-865); an interior node takes the union of its two children and the OR of
+// their sticky bits.  min / max of floats are exact, so the boxes are the builder's bit for bit.
+RT_HD void refit_node(const RefitArgs &A, uint32_t k) {
+    const uint32_t word = fbits(A.nodes[2 * (size_t)k + 1].z), cnt = word & 255u, lf = word >> 8;
+    f3 mn, mx;
+    bool sticky = false;
+    if (cnt) {
+        mn = mk(1e30f, 1e30f, 1e30f);
+        mx = mk(-1e30f, -1e30f, -1e30f);
+        for (uint32_t s = lf; s < lf + cnt; ++s) {
+            const float4 lo = A.slot_box[2 * (size_t)s], hi = A.slot_box[2 * (size_t)s + 1];
+            mn = fmin3(mn, mk(lo.x, lo.y, lo.z));
+            mx = fmax3(mx, mk(hi.x, hi.y, hi.z));
+            sticky = sticky || slot_sticky(lo);
+        }
+    } else {
+        const float4 *c = A.nodes + 2 * (size_t)lf;
+        const float4 l0 = c[0], l1 = c[1], r0 = c[2], r1 = c[3];
+        f3 lmn, lmx, rmn, rmx;
+        node_box(l0, l1, lmn, lmx);
+        node_box(r0, r1, rmn, rmx);
+        mn = fmin3(lmn, rmn);
+        mx = fmax3(lmx, rmx);
+        sticky = is_sticky(l1.w) || is_sticky(r1.w);
+    }
+    node_pack(mn, mx, word, walk_word(sticky, A.margin), A.nodes + 2 * (size_t)k);
+}
+// One height of a group: entries [lvl[l], lvl[l + 1]) of the list, dealt tid, tid + stride, ...
+// A group's heights run in order with a barrier between them (the nodes of a height read the
+// heights below); a host caller runs them in order with tid = 0, stride = 1.
+RT_HD void refit_level(const RefitArgs &A, uint32_t l, uint32_t tid, uint32_t stride) {
+    const uint32_t e = A.lvl[l + 1];
+    for (uint32_t i = A.lvl[l] + tid; i < e; i += stride) refit_node(A, A.list[i]);
+}
+
+}  // namespace rt

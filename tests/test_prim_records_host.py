@@ -1,7 +1,8 @@
-"""The every-kind record encoders of csrc/rt_records.h (what rt_scene_update_prims runs per primitive on
-the device) need no GPU: tests/cpp/prim_records_host.cpp re-encodes one primitive of each kind at a
-second pose and compares every record array with a fresh pack_scene of that pose, built with
-AddressSanitizer and UBSan as a stand-alone host program.  And the host refit over the animated room
+"""What rt_scene_update_prims runs per primitive on the device (PrimRecs and refit_level of
+csrc/rt_update.h, over the record encoders of csrc/rt_records.h) needs no GPU:
+tests/cpp/prim_records_host.cpp checks, writes and refits one primitive of each kind at a second pose
+and compares every array, the packed nodes included, with a fresh pack_scene of that pose, built
+with AddressSanitizer and UBSan as a stand-alone host program.  And the host refit over the animated room
 equals its numpy restatement; the compat header's new methods compile, link and report the library's
 error on a null handle."""
 import ctypes as C
