@@ -135,6 +135,8 @@ def lib():
         "rt_scene_update_prims": ([vp, u32, u32, vp, vp, vp], C.c_int),
         "rt_scene_update_prims_host": ([vp, u32, u32, C.POINTER(Prim), fp], C.c_int),
         "rt_scene_transform_triangles": ([vp, C.POINTER(TriXform), u32, vp, vp], C.c_int),
+        "rt_scene_rebuild": ([vp, vp], C.c_int),
+        "rt_scene_rebuild_stats": ([vp, C.POINTER(C.c_uint32)], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -591,6 +593,19 @@ class Scene:
             raise RTError(RT_ERR_INVALID, "transform_triangles: rest must hold 9 floats per triangle of the ranges")
         s = stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
         _check(self.L.rt_scene_transform_triangles(self.h, arr, len(ranges), C.c_void_p(v.data_ptr()), C.c_void_p(s)))
+
+    def rebuild(self, stream=None):
+        """rt_scene_rebuild: rebuild the plain BVH on the GPU from the scene's current primitives --
+        afterwards the scene equals a fresh one created from them (the tree build_bvh_host returns).
+        Blocks; render the next frame with reset = 1.  stream: a hipStream_t handle (None: the null stream)."""
+        _check(self.L.rt_scene_rebuild(self.h, C.c_void_p(stream)))
+
+    def rebuild_stats(self):
+        """rt_scene_rebuild_stats of the last rebuild: [tree levels of the many-workgroup path, nodes it
+        split, subtrees finished by the one-workgroup path, kernel launches]."""
+        out = (C.c_uint32 * 4)()
+        _check(self.L.rt_scene_rebuild_stats(self.h, out))
+        return [int(x) for x in out]
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

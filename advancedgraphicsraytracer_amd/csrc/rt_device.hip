@@ -276,6 +276,28 @@ int pack_options_from_env(PackOptions &o) {
     return RT_OK;
 }
 
+// Every scene field that follows from the tree, set here for a created scene and for a rebuilt one
+// (s->bvh's nodes_used, depth and max_leaf and the device node / slot arrays are already the tree's).
+// The camera-walk policy is not the tree's: creation derives it afterwards (scene_knobs_from_env), a
+// rebuild keeps it unless the new tree no longer admits the wave walk.
+void scene_tree_fields(rt_scene *s, uint32_t root_word, bool nested, bool bounds_finite) {
+    s->stack_depth = pick_stack(s->bvh.depth);
+    s->walk_fits = stack_admits_walk(s->stack_depth);
+    s->nested = nested;
+    SceneView &v = s->view;
+    v.nodes = (const float4 *)s->d_nodes;
+    v.prims = (const float4 *)s->d_prims;
+    v.root_word = root_word;
+    v.stack_entries = s->stack_depth;
+    v.bounds_finite = bounds_finite ? 1 : 0;
+    // XCD-grouped tile order for scenes whose nodes + primitive slots exceed one XCD's 4 MB L2:
+    // mig29 x16 (11.6 MB) 0.449 -> 0.406 ms; a cache-resident TEAPOT-F loses with it (4K
+    // 0.377 -> 0.441 ms, 720p neutral) -- profiles/r02/ab_xcd_*.json.  RT_XCD_ORDER=0/1 forces it.
+    s->xcd_order = (size_t)s->bvh.nodes_used * 32u + (size_t)s->num_prims * 48u > (4u << 20);
+    if (const char *e = std::getenv("RT_XCD_ORDER")) s->xcd_order = std::atoi(e) != 0;
+    if (s->walk != RT_WALK_LANE && !(s->nested && s->walk_fits)) s->walk = RT_WALK_LANE;
+}
+
 // the scene's launch policy: defaults from the tree, overridden by the environment (A/B runs)
 void scene_knobs_from_env(rt_scene *s) {
     // Primary+shadow frames read the nodes from global memory (L1/L2-resident, 256-thread
@@ -305,11 +327,6 @@ void scene_knobs_from_env(rt_scene *s) {
         const int k = std::atoi(e);
         s->split_parts = k >= 8 ? 8u : k >= 4 ? 4u : 2u;
     }
-    // XCD-grouped tile order for scenes whose nodes + primitive slots exceed one XCD's 4 MB L2:
-    // mig29 x16 (11.6 MB) 0.449 -> 0.406 ms; a cache-resident TEAPOT-F loses with it (4K
-    // 0.377 -> 0.441 ms, 720p neutral) -- profiles/r02/ab_xcd_*.json.  RT_XCD_ORDER=0/1 forces it.
-    s->xcd_order = (size_t)s->bvh.nodes_used * 32u + (size_t)s->num_prims * 48u > (4u << 20);
-    if (const char *e = std::getenv("RT_XCD_ORDER")) s->xcd_order = std::atoi(e) != 0;
     if (const char *e = std::getenv("RT_PT_PIPELINE")) s->pt_pipeline = std::atoi(e) != 0;
     if (const char *e = std::getenv("RT_PT_SLOTS")) s->pt_slots = (uint32_t)std::max(2, std::min((int)kPtMaxSlots, std::atoi(e)));
     if (const char *e = std::getenv("RT_PS_PIPELINE")) s->ps_pipeline = std::max(-1, std::min(1, std::atoi(e)));
@@ -338,11 +355,8 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     rt_scene *s = new rt_scene();
     s->device = d->device;
     s->num_prims = d->num_prims;
-    s->stack_depth = p.stack_depth;
     s->ext = p.ext;
     s->has_cubes = p.has_cubes;
-    s->nested = p.nested;
-    s->walk_fits = p.walk_fits;
     s->refit.boxes_finite = p.boxes_finite;
     s->quads = s->quad_lanes = p.has_quads;
     s->refit.sliver_lim = o.sliver_lim;
@@ -360,11 +374,11 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     s->bvh = std::move(p.bvh);
     s->refit.pinfo = std::move(p.pinfo);
     s->refit.pbox = std::move(p.pbox);
+    s->refit.pcen = std::move(p.pcen);
 
     SceneView &v = s->view;
     v = p.view;
-    v.nodes = (const float4 *)s->d_nodes;
-    v.prims = (const float4 *)s->d_prims;
+    scene_tree_fields(s, p.view.root_word, p.nested, p.view.bounds_finite != 0);
     v.shade = (const float4 *)s->d_shade;
     v.mats = (const DevMaterial *)s->d_mats;
     v.sky = (const uint32_t *)s->d_sky;
@@ -1455,18 +1469,15 @@ int rt_scene_set_camera_walk(rt_scene *s, int walk) {
 int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
     if (!cs || !nodes || !indices) return fail(RT_ERR_INVALID, "null argument");
     rt_scene *s = const_cast<rt_scene *>(cs);
-    if (s->refit.bvh_stale) {   // boxes refitted on the device since the last copy (updates block, so they are settled)
+    // boxes refitted, or the whole tree rebuilt, on the device since the last copy (both block, so they are settled)
+    if (s->refit.bvh_stale || s->refit.topo_stale) {
         HIP_TRY(hipSetDevice(s->device));
-        std::vector<float4> dn(2 * (size_t)s->bvh.nodes_used);
-        HIP_TRY(hipMemcpy(dn.data(), s->d_nodes, sizeof(float4) * dn.size(), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < s->bvh.nodes_used; ++i) {
-            Node &nd = s->bvh.nodes[i];
-            f3 mn, mx;
-            node_box(dn[2 * (size_t)i], dn[2 * (size_t)i + 1], mn, mx);
-            nd.mn[0] = mn.x; nd.mn[1] = mn.y; nd.mn[2] = mn.z;
-            nd.mx[0] = mx.x; nd.mx[1] = mx.y; nd.mx[2] = mx.z;
+        try {
+            const int rc = sync_host_tree(s->refit, s->bvh, s->d_nodes);
+            if (rc != RT_OK) return rc;
+        } catch (const std::exception &e) {
+            return fail(RT_ERR_INVALID, std::string("rt_scene_copy_bvh: ") + e.what());
         }
-        s->refit.bvh_stale = false;
     }
     std::memcpy(nodes, s->bvh.nodes.data(), sizeof(Node) * s->bvh.nodes_used);
     std::memcpy(indices, s->bvh.indices.data(), sizeof(uint32_t) * s->bvh.indices.size());
@@ -1489,7 +1500,7 @@ static int require_triangles(const rt_scene *s, uint32_t first, uint32_t count, 
             return fail(RT_ERR_INVALID, std::string(who) + ": primitive " + std::to_string(id) + " is not a triangle");
     return RT_OK;
 }
-static SceneRecords records_of(const rt_scene *s) {
+static SceneRecords records_of(rt_scene *s) {
     return SceneRecords{&s->bvh, s->num_prims, s->d_nodes, s->d_prims, s->d_shade, s->d_xprims, s->view.walk_margin};
 }
 // after an update: the scene's flags from the new root box
@@ -1625,6 +1636,48 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
     } catch (const std::exception &e) {
         return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
+}
+
+// ---- the rebuild (rt_build.hip): built into fresh buffers, checked, and only then swapped in
+int rt_scene_rebuild(rt_scene *s, void *stream) {
+    const char *who = "rt_scene_rebuild";
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_rebuild: null scene");
+    int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    // the builder's decisions are min / max over keys of the floats: a NaN box (kept from creation) has no place in them
+    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: a primitive's box is NaN or infinite");
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        Rebuilt t;
+        if ((rc = rebuild(s->refit, records_of(s), (hipStream_t)stream, t)) != RT_OK) return rc;
+        RefitState &R = s->refit;
+        for (void *old : {s->d_nodes, s->d_prims, R.d_slot_box, R.d_slot_of, R.d_index})
+            if (old) (void)hipFree(old);
+        s->d_nodes = t.nodes;
+        s->d_prims = t.prims;
+        R.d_slot_box = t.slot_box;
+        R.d_slot_of = t.slot_of;
+        R.d_index = t.index;
+        s->bvh.nodes_used = t.nodes_used;
+        s->bvh.depth = t.depth;
+        s->bvh.max_leaf = t.max_leaf;
+        // the host tree and the refit schedule are the old topology's: the tree is downloaded whole
+        // before its next use, the next update builds its schedule from it
+        R.topo_stale = true;
+        R.refit_ready = false;
+        for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
+        // every box is the union of the finite boxes below it
+        scene_tree_fields(s, t.root_word, true, t.finite);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {
+    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_rebuild_stats: null argument");
+    for (int k = 0; k < 4; ++k) out[k] = s->refit.rebuild_stats[k];
+    return RT_OK;
 }
 
 int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {

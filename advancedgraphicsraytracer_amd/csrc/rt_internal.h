@@ -65,10 +65,15 @@ struct ScenePack {            // everything scene_create computes before it touc
     // needs of the primitives that do not move
     std::vector<uint8_t> pinfo;
     std::vector<float> pbox;
+    std::vector<float> pcen;  // ... and its centroid (3 floats), what a rebuild bins by
     uint32_t stack_depth;     // LDS stack entries per lane
     bool ext, has_cubes, nested, walk_fits, boxes_finite, has_quads;
 };
 int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &out);
+// what follows from a tree's depth: the LDS stack entries per lane, and whether the wave walk's word
+// stack fits beside the lane stacks (take_tree; rt_scene_rebuild)
+uint32_t pick_stack(uint32_t depth);
+bool stack_admits_walk(uint32_t stack_depth);
 
 // frame size and device of a renderer (rt_multi.cpp)
 int renderer_geometry(const rt_renderer *r, uint32_t *W, uint32_t *H, int *device);

@@ -49,15 +49,22 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 
 // What a scene keeps for its updates and for nothing else.  Kept from creation: per primitive its
 // type | sticky << 7 (mark_sticky) and its box (prim_geometry; 6 floats) -- what a refit needs of
-// the primitives that do not move.  The plan and its device arrays are built by the first update;
-// the boxes and the schedule live on the device from there on.
+// the primitives that do not move -- and its centroid, which a rebuild bins by.  The first update or
+// rebuild puts slot map, slot boxes and centroids on the device, where they live from there on; the
+// schedule is built by the first update and again by the first after a rebuild (rt_build.hip).
 struct RefitState {
     std::vector<uint8_t> pinfo;
     std::vector<float> pbox;
+    std::vector<float> pcen;        // and its centroid (3 floats): what a rebuild bins by (rt_build.h)
     double sliver_lim = 0.0;        // mark_sticky's sine limit at creation (RT_WALK_STICKY)
     bool boxes_finite = true;       // every primitive box was finite at creation
-    bool refit_ready = false;
+    bool state_ready = false;       // slot_of, slot_box and cen are on the device (and authoritative from there on)
+    bool refit_ready = false;       // ... and so is the schedule of the current topology
     RefitPlan plan;
+    void *d_cen = nullptr;          // per id its centroid (float4)
+    void *d_index = nullptr;        // after a rebuild: the new primitive-index array (slot -> id)
+    bool topo_stale = false;        // a rebuild changed the topology: the host tree is downloaded whole before its next use
+    uint32_t rebuild_stats[4] = {0, 0, 0, 0};
     void *d_slot_of = nullptr, *d_slot_box = nullptr, *d_list = nullptr, *d_lvl = nullptr, *d_grp = nullptr, *d_flag = nullptr;
     bool bvh_stale = false;         // the device boxes are newer than the host tree (rt_scene_copy_bvh downloads them)
     void *d_ranges = nullptr;       // rt_scene_transform_triangles' range table (first, prefix counts, matrices)
@@ -67,7 +74,7 @@ void free_refit(RefitState &R);
 
 // the scene's side of an update: its tree and its device records
 struct SceneRecords {
-    const Bvh *bvh;
+    Bvh *bvh;
     uint32_t num_prims;
     void *nodes, *prims, *shade, *xprims;
     float margin;   // SceneView::walk_margin
@@ -110,5 +117,24 @@ int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hip
 // matrices[16 nr], uploaded to the scene's range table
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
                  hipStream_t st, const char *refusal, bool *finite);
+
+
+// the host tree from the device's after a refit (boxes) or a rebuild (nodes and indices)
+int sync_host_tree(RefitState &R, Bvh &b, const void *d_nodes);
+// slot_of, slot_box and the centroids on the device, from creation's host copies, once per scene
+int ensure_state(RefitState &R, const SceneRecords &S);
+
+// A rebuild's result (rt_build.hip): fresh device buffers for the caller to swap in, and the tree's figures.
+struct Rebuilt {
+    void *nodes = nullptr, *prims = nullptr, *slot_box = nullptr, *slot_of = nullptr, *index = nullptr;
+    uint32_t nodes_used = 0, depth = 0, max_leaf = 0, root_word = 0;
+    bool finite = false;
+    uint32_t stats[4] = {0, 0, 0, 0};
+};
+void free_rebuilt(Rebuilt &r);
+// Builds the tree rt_bvh_build_host would build for the scene's current primitives into fresh
+// buffers on `st`; blocks.  RT_ERR_UNSUPPORTED (nothing of the scene written, nothing left
+// allocated) when the tree breaks a kernel limit.
+int rebuild(RefitState &R, const SceneRecords &S, hipStream_t st, Rebuilt &out);
 
 }  // namespace rt

@@ -47,26 +47,28 @@ __device__ __forceinline__ void refit_group(const RefitArgs &A, uint32_t g) {
 __global__ void __launch_bounds__(256) k_refit_treelets(RefitArgs A) { refit_group(A, blockIdx.x); }
 __global__ void __launch_bounds__(1024) k_refit_top(RefitArgs A, uint32_t g) { refit_group(A, g); }
 
-// the refit plan and its device arrays, on the first update of a scene
+// the refit schedule of the current topology and its device arrays: on the first update of a scene
+// and on the first after a rebuild (the slot map, the slot boxes and the centroids stay the device's)
 int ensure_refit(RefitState &R, const SceneRecords &S) {
     if (R.refit_ready) return RT_OK;
+    int rc = sync_host_tree(R, *S.bvh, S.nodes);
+    if (rc != RT_OK) return rc;
     if (!build_refit_plan(*S.bvh, S.num_prims, R.plan)) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
-    std::vector<float4> box;
-    seed_slot_boxes(*S.bvh, R.pinfo, R.pbox, box);
-    int rc = upload(&R.d_slot_of, R.plan.slot_of);
-    if (rc == RT_OK) rc = upload(&R.d_slot_box, box);
-    if (rc == RT_OK) rc = upload(&R.d_list, R.plan.list);
+    if ((rc = ensure_state(R, S)) != RT_OK) return rc;
+    for (void **p : {&R.d_list, &R.d_lvl, &R.d_grp}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    rc = upload(&R.d_list, R.plan.list);
     if (rc == RT_OK) rc = upload(&R.d_lvl, R.plan.lvl);
     if (rc == RT_OK) rc = upload(&R.d_grp, R.plan.grp);
-    if (rc == RT_OK && !R.d_flag && hipMalloc(&R.d_flag, 16) != hipSuccess) rc = fail(RT_ERR_HIP, "hipMalloc failed");
     if (rc != RT_OK) {
-        for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp}) {
+        for (void **p : {&R.d_list, &R.d_lvl, &R.d_grp}) {
             if (*p) (void)hipFree(*p);
             *p = nullptr;
         }
         return rc;
     }
-    std::vector<float>().swap(R.pbox);   // the boxes and the schedule live on the device from here on
     for (std::vector<uint32_t> *v : {&R.plan.slot_of, &R.plan.list, &R.plan.lvl, &R.plan.grp}) std::vector<uint32_t>().swap(*v);
     R.refit_ready = true;
     return RT_OK;
@@ -80,13 +82,68 @@ RefitArgs refit_args(const RefitState &R, const SceneRecords &S) {
     A.lvl = (const uint32_t *)R.d_lvl; A.grp = (const uint32_t *)R.d_grp;
     A.margin = S.margin;
     A.sliver_lim = R.sliver_lim;
+    A.cen = (float4 *)R.d_cen;
     return A;
 }
 
 }  // namespace
 
+int ensure_state(RefitState &R, const SceneRecords &S) {
+    if (R.state_ready) return RT_OK;
+    // never updated, never rebuilt: the host tree and creation's per-primitive copies are current
+    std::vector<uint32_t> slot_of(S.num_prims, 0u);
+    if (S.bvh->indices.size() != S.num_prims) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
+    for (uint32_t k = 0; k < S.num_prims; ++k) {
+        if (S.bvh->indices[k] >= S.num_prims) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
+        slot_of[S.bvh->indices[k]] = k;
+    }
+    std::vector<float4> box, cen(S.num_prims);
+    seed_slot_boxes(*S.bvh, R.pinfo, R.pbox, box);
+    for (uint32_t i = 0; i < S.num_prims; ++i) cen[i] = make_float4(R.pcen[3 * (size_t)i], R.pcen[3 * (size_t)i + 1], R.pcen[3 * (size_t)i + 2], 0.0f);
+    int rc = upload(&R.d_slot_of, slot_of);
+    if (rc == RT_OK) rc = upload(&R.d_slot_box, box);
+    if (rc == RT_OK) rc = upload(&R.d_cen, cen);
+    if (rc == RT_OK && !R.d_flag && hipMalloc(&R.d_flag, 16) != hipSuccess) rc = fail(RT_ERR_HIP, "hipMalloc failed");
+    if (rc != RT_OK) {
+        for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_cen}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return rc;
+    }
+    std::vector<float>().swap(R.pbox);   // the boxes and the centroids live on the device from here on
+    std::vector<float>().swap(R.pcen);
+    R.state_ready = true;
+    return RT_OK;
+}
+
+int sync_host_tree(RefitState &R, Bvh &b, const void *d_nodes) {
+    if (!R.bvh_stale && !R.topo_stale) return RT_OK;
+    std::vector<float4> dn(2 * (size_t)b.nodes_used);
+    HIP_TRY(hipMemcpy(dn.data(), d_nodes, sizeof(float4) * dn.size(), hipMemcpyDeviceToHost));
+    if (R.topo_stale) {
+        b.nodes.assign(std::max<size_t>(2 * b.indices.size() + 2, b.nodes_used), Node{});
+        HIP_TRY(hipMemcpy(b.indices.data(), R.d_index, sizeof(uint32_t) * b.indices.size(), hipMemcpyDeviceToHost));
+    }
+    for (uint32_t i = 0; i < b.nodes_used; ++i) {
+        Node &nd = b.nodes[i];
+        f3 mn, mx;
+        node_box(dn[2 * (size_t)i], dn[2 * (size_t)i + 1], mn, mx);
+        nd.mn[0] = mn.x; nd.mn[1] = mn.y; nd.mn[2] = mn.z;
+        nd.mx[0] = mx.x; nd.mx[1] = mx.y; nd.mx[2] = mx.z;
+        if (R.topo_stale) {
+            const uint32_t word = fbits(dn[2 * (size_t)i + 1].z);
+            nd.leftFirst = word >> 8;
+            nd.count = word & 255u;
+        }
+    }
+    R.bvh_stale = R.topo_stale = false;
+    return RT_OK;
+}
+
 void free_refit(RefitState &R) {
-    for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp, &R.d_flag, &R.d_ranges}) {
+    R.state_ready = false;
+    for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp, &R.d_flag, &R.d_ranges, &R.d_cen, &R.d_index}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }

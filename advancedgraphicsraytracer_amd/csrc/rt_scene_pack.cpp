@@ -13,7 +13,6 @@
 #include "rt_refit.h"
 
 namespace rt {
-namespace {
 
 // LDS stack entries per lane: a traversal pushes at most one entry per tree level, so the tree
 // depth is enough.  Rounding it up to 8 cost occupancy where the stacks bound the workgroups
@@ -27,6 +26,9 @@ uint32_t pick_stack(uint32_t depth) {   // entries needed <= tree depth (rounded
     uint32_t need = depth < 2 ? 2 : depth;
     return (need + RT_STACK_ROUND - 1u) / RT_STACK_ROUND * RT_STACK_ROUND;
 }
+// trees deeper than 60: the lane stacks (depth x 1 KB) leave no room for the walk's words
+bool stack_admits_walk(uint32_t stack_depth) { return (size_t)stack_depth * (256u + 4u) * sizeof(uint32_t) <= kLdsLaunchMax; }
+namespace {
 
 // Two-level node records (the path tracer's lane kernel, k_pt_lanes<.., true>): one 128-B
 // record per interior node x at even depth (the root at 0) holding the node entries of x's
@@ -202,8 +204,7 @@ int take_tree(const rt_scene_desc *d, const PackOptions &o, ScenePack &s, TreeWa
     if (b.max_leaf > 255) return fail(RT_ERR_UNSUPPORTED, "BVH leaf with more than 255 primitives");
     if (b.depth > 64) return fail(RT_ERR_UNSUPPORTED, "BVH deeper than 64 (the reference's stack[64])");
     s.stack_depth = pick_stack(b.depth);
-    // trees deeper than 60: the lane stacks (depth x 1 KB) leave no room for the walk's words
-    s.walk_fits = (size_t)s.stack_depth * (256u + 4u) * sizeof(uint32_t) <= kLdsLaunchMax;
+    s.walk_fits = stack_admits_walk(s.stack_depth);
     return RT_OK;
 }
 
@@ -240,6 +241,7 @@ void pack_nodes(const rt_scene_desc *d, const PackOptions &o, const std::vector<
     }
     const uint32_t n = d->num_prims;
     s.pbox.resize(6 * (size_t)n);
+    s.pcen.resize(3 * (size_t)n);
     s.boxes_finite = true;
     for (uint32_t id = 0; id < n; ++id) {
         PrimX x;
@@ -251,6 +253,7 @@ void pack_nodes(const rt_scene_desc *d, const PackOptions &o, const std::vector<
             s.pbox[6 * (size_t)id + c] = bx[c];
             if (!std::isfinite(bx[c])) s.boxes_finite = false;
         }
+        s.pcen[3 * (size_t)id] = g.centroid.x; s.pcen[3 * (size_t)id + 1] = g.centroid.y; s.pcen[3 * (size_t)id + 2] = g.centroid.z;
         s.pinfo[id] = (uint8_t)(d->prims[id].type | (s.pinfo[id] ? 0x80 : 0));
     }
 }

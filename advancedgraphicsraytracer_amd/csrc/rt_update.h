@@ -22,6 +22,7 @@ struct RefitArgs {
     const uint32_t *slot_of, *list, *lvl, *grp;   // the refit plan (RefitPlan, rt_refit.h)
     float margin;                    // SceneView::walk_margin
     double sliver_lim;               // mark_sticky's sine limit
+    float4 *cen;                     // per primitive id its centroid, what a rebuild bins by (rt_build.h); null: not kept
 };
 
 RT_HD bool finite_f(float f) { return (fbits(f) & 0x7f800000u) != 0x7f800000u; }
@@ -43,6 +44,11 @@ RT_HD void write_tri(const RefitArgs &A, uint32_t id, const float w[9]) {
     f3 mn, mx;
     tri_box(w, mn, mx);
     slot_box(mn, mx, tri_sliver(w, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
+    if (A.cen) {   // prim_geometry's triangle centroid
+        const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        const f3 c = tpos(I, ((mk(w[0], w[1], w[2]) + mk(w[3], w[4], w[5])) + mk(w[6], w[7], w[8])) / 3.0f);
+        A.cen[id] = make_float4(c.x, c.y, c.z, 0.0f);
+    }
 }
 
 // rt_scene_update_triangles: triangle first + i from the nine floats at verts + 9 i
@@ -147,6 +153,7 @@ struct PrimRecs {
         if (p.type == RT_CUBE || p.type == RT_QUAD) prim_xentry(p, x, A.xprims + 8 * (size_t)xi);
         const bool sticky = p.type == RT_TRIANGLE ? tri_sliver(p.v, A.sliver_lim) : slot_sticky(A.slot_box[2 * (size_t)slot]);
         slot_box(g.bmin, g.bmax, sticky, A.slot_box + 2 * (size_t)slot);
+        if (A.cen) A.cen[id] = make_float4(g.centroid.x, g.centroid.y, g.centroid.z, 0.0f);
     }
 };
 

@@ -200,7 +200,8 @@ int rt_scene_get_info(const rt_scene *s, rt_scene_info *info);
 enum { RT_WALK_LANE = 0, RT_WALK_WAVE = 1, RT_WALK_AUTO = 2 };
 int rt_scene_set_camera_walk(rt_scene *s, int walk);
 /* host copy of the BVH in use (nodes_used x 32 B, num_refs x u32), in the reference's node order;
- * after rt_scene_update_triangles the first call downloads the refitted boxes */
+ * after an in-place update the first call downloads the refitted boxes, after rt_scene_rebuild the
+ * new nodes and indices */
 int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
 /* Animated geometry (the reference's "optionally animated" scene: Scene::SetTime, template/scene.h:213-224,
  * and Tick's animation branch, renderer.cpp:206-237).  Replace the vertices of triangle primitives
@@ -219,7 +220,8 @@ int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
  *                       checked in a pass of their own before anything is written);
  *   RT_ERR_UNSUPPORTED  an SBVH scene (num_refs != num_prims), or one built with RT_PT_QUADS=1.
  * count == 0 is RT_OK and does nothing.  Other kinds and the light move with rt_scene_update_prims,
- * whole meshes by matrix with rt_scene_transform_triangles; topology changes need a new scene. */
+ * whole meshes by matrix with rt_scene_transform_triangles; the topology changes with rt_scene_rebuild
+ * alone (adding or removing primitives needs a new scene). */
 int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream);
 /* the same with the vertices in host memory (staged on the scene's private stream) */
 int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts);
@@ -257,6 +259,23 @@ int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, cons
 typedef struct { uint32_t first, count; float M[16]; } rt_tri_xform;
 int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
                                  void *stream);
+/* Rebuild the scene's plain BVH on the GPU from its CURRENT primitives (after any number of
+ * in-place updates): afterwards the scene is bit for bit a fresh rt_scene_create of the current
+ * description -- node array, primitive-index array, leaf-slot records in the new slot order,
+ * sticky words, root word, stack depth, walk eligibility, bounds_finite -- i.e. the tree
+ * rt_bvh_build_host returns for those primitives.  Blocks like the update calls (waits for the
+ * scene's device, runs on `stream`, returns when the scene is ready for any stream).  The caller
+ * renders the next frame with reset = 1 (exact-distance ties may resolve differently on a new tree).
+ *   RT_ERR_UNSUPPORTED  an SBVH or RT_PT_QUADS=1 scene; a scene created with a NaN or infinite
+ *                       primitive box; or the new tree breaks a kernel limit (leaf > 255,
+ *                       depth > 64, > 2^24 nodes) -- the scene is untouched;
+ *   RT_ERR_INVALID      null scene.
+ * Renderers keep their timed choices and tile orders; the scene keeps its camera-walk policy where
+ * the new tree still admits it.  The next in-place update rebuilds its refit schedule. */
+int rt_scene_rebuild(rt_scene *s, void *stream);
+/* diagnostics of the last rebuild: out[0] tree levels processed, out[1] nodes split by the
+ * many-workgroup path, out[2] subtrees finished by the one-workgroup path, out[3] kernel launches */
+int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]);
 
 /* Batched Scene::IntersectBVH (template/scene.h:285-320): rays_dev[n] -> hits_dev[n]. */
 int rt_intersect(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, uint32_t n, void *stream);

@@ -289,6 +289,9 @@ class Scene {   // template/scene.h:37
     void TransformTriangles(const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev, void *stream = nullptr) {
         rt_check(rt_scene_transform_triangles(handle(), ranges, num_ranges, rest_dev, stream));
     }
+    // Scene::BuildBVH (template/scene.h:845): the tree of the current primitives, rebuilt on the GPU after
+    // in-place updates have moved them; the next Tick resets the accumulator
+    void BuildBVH(void *stream = nullptr) { rt_check(rt_scene_rebuild(handle(), stream)); }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
