@@ -137,6 +137,8 @@ def lib():
         "rt_scene_transform_triangles": ([vp, C.POINTER(TriXform), u32, vp, vp], C.c_int),
         "rt_scene_rebuild": ([vp, vp], C.c_int),
         "rt_scene_rebuild_stats": ([vp, C.POINTER(C.c_uint32)], C.c_int),
+        "rt_scene_splice_triangles": ([vp, u32, u32, vp, u32, vp], C.c_int),
+        "rt_scene_splice_triangles_host": ([vp, u32, u32, C.POINTER(Prim), u32], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -606,6 +608,28 @@ class Scene:
         out = (C.c_uint32 * 4)()
         _check(self.L.rt_scene_rebuild_stats(self.h, out))
         return [int(x) for x in out]
+
+    def splice_triangles(self, first, remove, prims, stream=None):
+        """rt_scene_splice_triangles: triangle primitives [first, first + remove) leave, the triangles of
+        `prims` enter at id `first` (first == num_prims appends), and the tree is rebuilt on the GPU --
+        afterwards the scene equals a fresh one created from the spliced list.  prims: a list of
+        triangle() records (staged by the library), or a torch tensor [count, 11] of 32-bit words on the
+        scene's device, laid out as pack_prims does.  Ids behind the edit shift by len(prims) - remove.
+        Blocks; render the next frame with reset=True."""
+        torch = _torch()
+        if isinstance(prims, torch.Tensor):
+            if not prims.is_cuda or prims.device.index != self.device:
+                raise RTError(RT_ERR_INVALID, "splice_triangles: the tensor must be on the scene's device")
+            if prims.element_size() != 4 or prims.dim() != 2 or prims.shape[1] != 11:
+                raise RTError(RT_ERR_INVALID, "splice_triangles: records must be [count, 11] 32-bit words")
+            rec = prims.contiguous()
+            s = stream if stream is not None else torch.cuda.current_stream(rec.device).cuda_stream
+            _check(self.L.rt_scene_splice_triangles(self.h, first, remove, C.c_void_p(rec.data_ptr()) if rec.shape[0] else None,
+                                                    rec.shape[0], C.c_void_p(s)))
+            return
+        prims = list(prims)
+        arr = (Prim * len(prims))(*prims) if prims else None
+        _check(self.L.rt_scene_splice_triangles_host(self.h, first, remove, arr, len(prims)))
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

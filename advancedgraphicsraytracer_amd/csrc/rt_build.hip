@@ -1,4 +1,5 @@
-// rt_build.hip -- the GPU BVH rebuild: the kernels and the host path of rt::rebuild.
+// rt_build.hip -- the GPU BVH rebuild: the kernels and the host path, rt::build_tree
+// over given inputs (rt::splice builds over a new id space with it) and rt::rebuild over the scene's own.
 //
 // rt_build.h holds every line a lane runs; the kernels here supply the lane context (lane index,
 // __syncthreads, integer atomics) and the launch order:
@@ -22,6 +23,7 @@
 #include "rt_refit.h"
 
 #include <cmath>
+#include <string>
 
 namespace rt {
 
@@ -123,7 +125,7 @@ void carve(Arena &a, uint32_t n, BuildArgs &B) {
     B.depth_of = a.take<uint32_t>(2 * (size_t)n + 2);
 }
 
-int run_build(const BuildArgs &B, hipStream_t st, Rebuilt &out) {
+int run_build(const BuildArgs &B, hipStream_t st, const std::string &who, Rebuilt &out) {
     const uint32_t n = B.n;
     const dim3 block(256);
     const dim3 per_prim((n + 255u) / 256u);
@@ -136,8 +138,8 @@ int run_build(const BuildArgs &B, hipStream_t st, Rebuilt &out) {
     HIP_TRY(hipMemcpyAsync(lvl, B.ctr + kCtrLevel, sizeof(lvl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t lv = 0; lvl[0] > 0; ++lv) {
-        if (lv > kBuildMaxDepth) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the new tree is deeper than 64");
-        if (lvl[0] > build_wide_cap(n) || lvl[1] > build_task_cap(n)) return fail(RT_ERR_HIP, "rt_scene_rebuild: level tables overrun");
+        if (lv > kBuildMaxDepth) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64");
+        if (lvl[0] > build_wide_cap(n) || lvl[1] > build_task_cap(n)) return fail(RT_ERR_HIP, who + ": level tables overrun");
         const dim3 tasks(lvl[1]);
         HIP_TRY(hipMemsetAsync(B.wacc, 0, sizeof(uint32_t) * kAccWords * (size_t)lvl[0], st));
         hipLaunchKernelGGL(k_wide_bounds, tasks, block, 0, st, B, lv);
@@ -157,7 +159,7 @@ int run_build(const BuildArgs &B, hipStream_t st, Rebuilt &out) {
     HIP_TRY(hipMemcpyAsync(ctr, B.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint32_t nsmall = ctr[kCtrSmall];
-    if (nsmall > n) return fail(RT_ERR_HIP, "rt_scene_rebuild: subtree list overrun");
+    if (nsmall > n) return fail(RT_ERR_HIP, who + ": subtree list overrun");
     if (nsmall) {
         hipLaunchKernelGGL(k_subtrees, dim3(nsmall), block, 0, st, B);
         ++launches;
@@ -176,9 +178,9 @@ int run_build(const BuildArgs &B, hipStream_t st, Rebuilt &out) {
     out.depth = ctr[kCtrDepth];
     out.max_leaf = ctr[kCtrMaxLeaf];
     if ((ctr[kCtrErr] & kBuildErrDepth) || out.depth > kBuildMaxDepth)
-        return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the new tree is deeper than 64 (the reference's stack[64])");
-    if (out.max_leaf > 255) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the new tree has a leaf with more than 255 primitives");
-    if (out.nodes_used > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: the new tree has more than 2^24 nodes");
+        return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64 (the reference's stack[64])");
+    if (out.max_leaf > 255) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has a leaf with more than 255 primitives");
+    if (out.nodes_used > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has more than 2^24 nodes");
     hipLaunchKernelGGL(k_permute, per_prim, block, 0, st, B);
     ++launches;
     const dim3 per_node((out.nodes_used + 255u) / 256u);
@@ -203,30 +205,27 @@ int run_build(const BuildArgs &B, hipStream_t st, Rebuilt &out) {
 }  // namespace
 
 void free_rebuilt(Rebuilt &r) {
-    for (void **p : {&r.nodes, &r.prims, &r.slot_box, &r.slot_of, &r.index}) {
+    for (void **p : {&r.nodes, &r.prims, &r.slot_box, &r.slot_of, &r.index, &r.shade, &r.cen}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
 }
 
-int rebuild(RefitState &R, const SceneRecords &S, hipStream_t st, Rebuilt &out) {
-    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
-    int rc = sync_host_tree(R, *S.bvh, S.nodes);   // a scene never updated seeds its state from the host tree
-    if (rc == RT_OK) rc = ensure_state(R, S);
-    if (rc != RT_OK) return rc;
-    const uint32_t n = S.num_prims;
+int build_tree(const BuildInputs &in, hipStream_t st, Rebuilt &out) {
+    const uint32_t n = in.n;
+    const std::string who = in.who;
     BuildArgs B{};
     B.n = n;
-    B.cen = (const float4 *)R.d_cen;
-    B.old_box = (const float4 *)R.d_slot_box;
-    B.old_slot_of = (const uint32_t *)R.d_slot_of;
-    B.old_prims = (const float4 *)S.prims;
-    B.margin = S.margin;
+    B.cen = (const float4 *)in.cen;
+    B.old_box = (const float4 *)in.box;
+    B.old_slot_of = (const uint32_t *)in.slot_of;
+    B.old_prims = (const float4 *)in.prims;
+    B.margin = in.margin;
     Arena sizes;
     carve(sizes, n, B);
     void *work = nullptr;
-    auto alloc = [](void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? RT_OK : fail(RT_ERR_HIP, "rt_scene_rebuild: hipMalloc failed"); };
-    rc = alloc(&work, sizes.used);
+    auto alloc = [&who](void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? RT_OK : fail(RT_ERR_HIP, who + ": hipMalloc failed"); };
+    int rc = alloc(&work, sizes.used);
     if (rc == RT_OK) rc = alloc(&out.nodes, sizeof(float4) * 2 * (2 * (size_t)n + 2));
     if (rc == RT_OK) rc = alloc(&out.prims, sizeof(float4) * 3 * (size_t)n);
     if (rc == RT_OK) rc = alloc(&out.slot_box, sizeof(float4) * 2 * (size_t)n);
@@ -241,12 +240,20 @@ int rebuild(RefitState &R, const SceneRecords &S, hipStream_t st, Rebuilt &out) 
         B.prims = (float4 *)out.prims;
         B.slot_box = (float4 *)out.slot_box;
         B.slot_of = (uint32_t *)out.slot_of;
-        rc = run_build(B, st, out);
+        rc = run_build(B, st, who, out);
         if (rc != RT_OK) (void)hipStreamSynchronize(st);
     }
     if (work) (void)hipFree(work);
     if (rc != RT_OK) free_rebuilt(out);
     return rc;
+}
+
+int rebuild(RefitState &R, const SceneRecords &S, hipStream_t st, Rebuilt &out) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
+    int rc = sync_host_tree(R, *S.bvh, S.nodes);   // a scene never updated seeds its state from the host tree
+    if (rc == RT_OK) rc = ensure_state(R, S);
+    if (rc != RT_OK) return rc;
+    return build_tree(BuildInputs{S.num_prims, R.d_cen, R.d_slot_box, R.d_slot_of, S.prims, S.margin, "rt_scene_rebuild"}, st, out);
 }
 
 }  // namespace rt

@@ -35,6 +35,7 @@
 #include "rt_internal.h"
 #include "rt_records.h"
 #include "rt_refit.h"
+#include "rt_splice.h"
 #include "rt_tune.h"
 
 // ====================================================================== host side
@@ -45,6 +46,7 @@ struct rt_scene {
     SceneView view{};
     Bvh bvh;
     uint32_t num_prims = 0;
+    uint32_t num_materials = 0; // what an inserted triangle's material index is checked against
     uint32_t stack_depth = 0;   // LDS stack entries per lane
     int frame_waves = 0;        // primary+shadow frame kernel build (frame_build): 0 = chosen, 7 = the
                                 // plain build, 8 = the single-sample one wherever it applies (RT_FRAME_WAVES)
@@ -355,6 +357,7 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     rt_scene *s = new rt_scene();
     s->device = d->device;
     s->num_prims = d->num_prims;
+    s->num_materials = d->num_materials;
     s->ext = p.ext;
     s->has_cubes = p.has_cubes;
     s->refit.boxes_finite = p.boxes_finite;
@@ -1672,6 +1675,95 @@ int rt_scene_rebuild(rt_scene *s, void *stream) {
     } catch (const std::exception &e) {
         return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
+}
+
+// ---- the splice (rt_splice.hip): triangles leave and enter; the new id space and its tree are made
+// in fresh buffers, checked, and only then swapped in
+
+// every refusal that needs no device, in the order the header lists them; *empty: nothing to do
+static int splice_arguments(const rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert,
+                            const char *who, bool *empty) {
+    const std::string w = who;
+    *empty = false;
+    uint32_t bad = 0;
+    const int k = splice_range(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, first, remove, insert, prims, &bad);
+    if (k == kSpliceLight) return fail(RT_ERR_INVALID, w + ": first = 0 (primitive 0 is the light and stays)");
+    if (k == kSpliceNull) return fail(RT_ERR_INVALID, w + ": null records");
+    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
+    if (k == kSpliceRange) return fail(RT_ERR_INVALID, w + ": range outside the primitives");
+    if (remove == 0 && insert == 0) {
+        *empty = true;
+        return RT_OK;
+    }
+    const int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
+    if (k == kSpliceKind) return fail(RT_ERR_INVALID, w + ": primitive " + std::to_string(bad) + " is not a triangle");
+    if ((uint64_t)s->num_prims - remove + insert >= (1u << 24)) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 primitives");
+    return RT_OK;
+}
+
+int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert,
+                              void *stream) {
+    const char *who = "rt_scene_splice_triangles";
+    bool empty = false;
+    int rc = splice_arguments(s, first, remove, prims_dev, insert, who, &empty);
+    if (rc != RT_OK || empty) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    Rebuilt t;
+    try {
+        const uint32_t n = s->num_prims - remove + insert;
+        // the host's share, made before anything is swapped: the type bytes require_triangles reads
+        // and an index array of the new size (sync_host_tree sizes its download from it)
+        RefitState &R = s->refit;
+        std::vector<uint8_t> pinfo;
+        pinfo.reserve(n);
+        pinfo.insert(pinfo.end(), R.pinfo.begin(), R.pinfo.begin() + first);
+        pinfo.insert(pinfo.end(), insert, (uint8_t)RT_TRIANGLE);
+        pinfo.insert(pinfo.end(), R.pinfo.begin() + first + remove, R.pinfo.end());
+        std::vector<uint32_t> indices(n, 0u);
+        const SpliceEdit e{first, remove, insert, prims_dev, s->num_materials};
+        if ((rc = splice(R, records_of(s), e, (hipStream_t)stream, t)) != RT_OK) return rc;
+        for (void *old : {s->d_nodes, s->d_prims, s->d_shade, R.d_slot_box, R.d_slot_of, R.d_index, R.d_cen})
+            if (old) (void)hipFree(old);
+        s->d_nodes = t.nodes;
+        s->d_prims = t.prims;
+        s->d_shade = t.shade;
+        R.d_slot_box = t.slot_box;
+        R.d_slot_of = t.slot_of;
+        R.d_index = t.index;
+        R.d_cen = t.cen;
+        s->num_prims = n;
+        R.pinfo.swap(pinfo);
+        s->bvh.indices.swap(indices);
+        s->bvh.nodes_used = t.nodes_used;
+        s->bvh.depth = t.depth;
+        s->bvh.max_leaf = t.max_leaf;
+        // as after a rebuild: the host tree is downloaded whole before its next use, the next update
+        // builds its schedule from it
+        R.topo_stale = true;
+        R.refit_ready = false;
+        for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
+        s->view.shade = (const float4 *)s->d_shade;
+        scene_tree_fields(s, t.root_word, true, t.finite);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        free_rebuilt(t);
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert) {
+    bool empty = false;
+    int rc = splice_arguments(s, first, remove, prims, insert, "rt_scene_splice_triangles_host", &empty);
+    if (rc != RT_OK || empty) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    if (insert) {
+        HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+        if ((rc = grow(&s->d_scratch, &s->scratch_bytes, sizeof(rt_prim) * (size_t)insert)) != RT_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(s->d_scratch, prims, sizeof(rt_prim) * (size_t)insert, hipMemcpyHostToDevice, s->stream));
+    }
+    return rt_scene_splice_triangles(s, first, remove, insert ? (const rt_prim *)s->d_scratch : nullptr, insert, s->stream);
 }
 
 int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {

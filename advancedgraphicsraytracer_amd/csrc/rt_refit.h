@@ -127,14 +127,37 @@ int ensure_state(RefitState &R, const SceneRecords &S);
 // A rebuild's result (rt_build.hip): fresh device buffers for the caller to swap in, and the tree's figures.
 struct Rebuilt {
     void *nodes = nullptr, *prims = nullptr, *slot_box = nullptr, *slot_of = nullptr, *index = nullptr;
+    void *shade = nullptr, *cen = nullptr;   // a splice's new id space (rt_splice.hip); a rebuild leaves them null
     uint32_t nodes_used = 0, depth = 0, max_leaf = 0, root_word = 0;
     bool finite = false;
     uint32_t stats[4] = {0, 0, 0, 0};
 };
 void free_rebuilt(Rebuilt &r);
-// Builds the tree rt_bvh_build_host would build for the scene's current primitives into fresh
-// buffers on `st`; blocks.  RT_ERR_UNSUPPORTED (nothing of the scene written, nothing left
-// allocated) when the tree breaks a kernel limit.
+// What the builder reads, all on the device: per id the centroid (float4), per old leaf slot the box
+// (2 float4) and the leaf-slot record (3 float4), and id -> old slot.  who: the entry point, for messages.
+struct BuildInputs {
+    uint32_t n;
+    const void *cen, *box, *slot_of, *prims;
+    float margin;
+    const char *who;
+};
+// Builds the tree rt_bvh_build_host would build for those primitives into fresh buffers on `st`
+// (nodes, prims, slot_box, slot_of and index of `out`); blocks.  RT_ERR_UNSUPPORTED when the tree
+// breaks a kernel limit; after any error every buffer of `out` is freed.
+int build_tree(const BuildInputs &in, hipStream_t st, Rebuilt &out);
+// The same for the scene's current primitives.  Nothing of the scene is written.
 int rebuild(RefitState &R, const SceneRecords &S, hipStream_t st, Rebuilt &out);
+
+// rt_scene_splice_triangles (rt_splice.hip): ids [first, first + remove) leave, `insert` triangles
+// (recs_dev: DEVICE rt_prim) enter at id `first`
+struct SpliceEdit {
+    uint32_t first, remove, insert;
+    const rt_prim *recs_dev;
+    uint32_t num_materials;
+};
+// Checks the inserted records (RT_ERR_INVALID), forms the new id space in fresh buffers (shade and
+// cen of `out`) and builds its tree (build_tree) on `st`; blocks.  Nothing of the scene is written,
+// and after any error nothing is left allocated.
+int splice(RefitState &R, const SceneRecords &S, const SpliceEdit &E, hipStream_t st, Rebuilt &out);
 
 }  // namespace rt

@@ -34,6 +34,12 @@ RT_HD bool tri_ok(const float w[9]) {
     for (int k = 0; k < 9; ++k) ok = ok && finite_f(w[k]);
     return ok;
 }
+// prim_geometry's triangle centroid
+RT_HD float4 tri_centroid(const float w[9]) {
+    const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const f3 c = tpos(I, ((mk(w[0], w[1], w[2]) + mk(w[3], w[4], w[5])) + mk(w[6], w[7], w[8])) / 3.0f);
+    return make_float4(c.x, c.y, c.z, 0.0f);
+}
 // the rt_records.h encoders that scene creation runs, so the records equal those of a fresh
 // rt_scene_create on the new vertices; the material word of the shading record stays
 RT_HD void write_tri(const RefitArgs &A, uint32_t id, const float w[9]) {
@@ -44,11 +50,7 @@ RT_HD void write_tri(const RefitArgs &A, uint32_t id, const float w[9]) {
     f3 mn, mx;
     tri_box(w, mn, mx);
     slot_box(mn, mx, tri_sliver(w, A.sliver_lim), A.slot_box + 2 * (size_t)slot);
-    if (A.cen) {   // prim_geometry's triangle centroid
-        const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        const f3 c = tpos(I, ((mk(w[0], w[1], w[2]) + mk(w[3], w[4], w[5])) + mk(w[6], w[7], w[8])) / 3.0f);
-        A.cen[id] = make_float4(c.x, c.y, c.z, 0.0f);
-    }
+    if (A.cen) A.cen[id] = tri_centroid(w);
 }
 
 // rt_scene_update_triangles: triangle first + i from the nine floats at verts + 9 i

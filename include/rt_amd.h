@@ -220,8 +220,8 @@ int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
  *                       checked in a pass of their own before anything is written);
  *   RT_ERR_UNSUPPORTED  an SBVH scene (num_refs != num_prims), or one built with RT_PT_QUADS=1.
  * count == 0 is RT_OK and does nothing.  Other kinds and the light move with rt_scene_update_prims,
- * whole meshes by matrix with rt_scene_transform_triangles; the topology changes with rt_scene_rebuild
- * alone (adding or removing primitives needs a new scene). */
+ * whole meshes by matrix with rt_scene_transform_triangles; the topology changes with rt_scene_rebuild,
+ * the number of triangles with rt_scene_splice_triangles. */
 int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream);
 /* the same with the vertices in host memory (staged on the scene's private stream) */
 int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts);
@@ -276,6 +276,38 @@ int rt_scene_rebuild(rt_scene *s, void *stream);
 /* diagnostics of the last rebuild: out[0] tree levels processed, out[1] nodes split by the
  * many-workgroup path, out[2] subtrees finished by the one-workgroup path, out[3] kernel launches */
 int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]);
+/* Add and remove triangles in a live scene.  Remove triangle primitives [first, first + remove) and
+ * insert `insert` new triangles at id `first`; primitives behind the edit shift by insert - remove.
+ * prims_dev: DEVICE rt_prim[insert] (type RT_TRIANGLE, v[0..8] world-space A, B, C, material an index
+ * of the scene's materials).  first == num_prims appends.  Afterwards the scene is bit for bit a fresh
+ * rt_scene_create of the spliced description -- the old primitive list with the range erased and the
+ * new records inserted at `first`; materials, textures, sky and transforms as they were -- in
+ * everything the kernels read: node array, primitive-index array, leaf-slot records in the new slot
+ * order with the NEW ids in them, shading records per new id, sticky words, root word, stack depth,
+ * walk eligibility, bounds_finite, and rt_scene_get_info.  The tree is the one rt_bvh_build_host
+ * returns for the spliced list (also where the scene was created with a prebuilt BVH).  Blocks like
+ * the update calls (waits for the scene's device, runs on `stream`, returns when the scene is ready
+ * for any stream); the caller renders the next frame with reset = 1.  Renderers stay valid and keep
+ * their accumulator buffers, tile orders and timed choices; the scene keeps its camera-walk policy
+ * where the new tree admits it.  The next in-place update rebuilds its refit schedule.
+ * Ids the caller holds for later rt_scene_update_triangles, rt_scene_transform_triangles or
+ * rt_scene_update_prims calls shift with the edit: every id >= first + remove moves by
+ * insert - remove.  That bookkeeping is the caller's.
+ * Only triangles enter and leave; primitives of other kinds may sit anywhere, also behind the edit.
+ *   RT_ERR_INVALID      null scene, or null records with insert > 0; first == 0 (primitive 0 is the
+ *                       light and stays); first + remove > num_prims; a non-triangle in the removed
+ *                       range; an inserted record that is no RT_TRIANGLE, whose material is outside
+ *                       [0, num_materials), or with a NaN / infinite vertex (checked in a pass of its
+ *                       own before anything is written);
+ *   RT_ERR_UNSUPPORTED  an SBVH or RT_PT_QUADS=1 scene; a scene created with a NaN or infinite
+ *                       primitive box; 2^24 primitives or more; or the new tree breaks a kernel limit
+ *                       (leaf > 255, depth > 64, > 2^24 nodes);
+ *   RT_ERR_HIP          an allocation failed.
+ * After every refusal the scene is untouched.  remove == 0 && insert == 0 is RT_OK and does nothing. */
+int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert,
+                              void *stream);
+/* the same with the records in host memory (staged on the scene's private stream) */
+int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert);
 
 /* Batched Scene::IntersectBVH (template/scene.h:285-320): rays_dev[n] -> hits_dev[n]. */
 int rt_intersect(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, uint32_t n, void *stream);

@@ -292,6 +292,17 @@ class Scene {   // template/scene.h:37
     // Scene::BuildBVH (template/scene.h:845): the tree of the current primitives, rebuilt on the GPU after
     // in-place updates have moved them; the next Tick resets the accumulator
     void BuildBVH(void *stream = nullptr) { rt_check(rt_scene_rebuild(handle(), stream)); }
+    // A mesh enters or leaves, or is swapped for one of another size, without a new Scene: triangle
+    // primitives [first, first + remove) go, `insert` new ones (rt_prim records in host memory) come in at
+    // id `first`, and the tree is rebuilt on the GPU.  Ids behind the edit shift by insert - remove; the
+    // next Tick resets the accumulator
+    void SpliceTriangles(uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert) {
+        rt_check(rt_scene_splice_triangles_host(handle(), first, remove, prims, insert));
+    }
+    // the same with the records already in device memory, on a hipStream_t
+    void SpliceTrianglesDevice(uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert, void *stream = nullptr) {
+        rt_check(rt_scene_splice_triangles(handle(), first, remove, prims_dev, insert, stream));
+    }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
