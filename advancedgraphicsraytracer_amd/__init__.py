@@ -30,11 +30,13 @@ DIFFUSE, MIRROR, DIELECTRIC, CHECKERBOARD, LIGHT, DSMIX, TEXTURE = 0, 1, 2, 3, 4
 MODE_PATH = 0
 MODE_WHITTED = 1
 MODE_PACKET = 2
+MODE_BVH_HEAT = 3   # the BVH_ANALYSIS build of Tick: Scene::BVHVisualization per sample (renderer.cpp:224-226)
 WALK_LANE, WALK_WAVE, WALK_AUTO = 0, 1, 2
 WALK_CHECK_OFF, WALK_CHECK_COUNT, WALK_CHECK_VERIFY = 0, 1, 2
 BVH_PLAIN, BVH_SBVH = 0, 1
 # renderer.h:9, renderer.h:13, renderer.cpp:105 (TracePacket's bounces: Trace's default depth)
-DEFAULT_DEPTH = {MODE_PATH: 10, MODE_WHITTED: 20, MODE_PACKET: 10}
+# (a heat frame ignores its depth: the kernel divides by the tree's)
+DEFAULT_DEPTH = {MODE_PATH: 10, MODE_WHITTED: 20, MODE_PACKET: 10, MODE_BVH_HEAT: 1}
 RECIPES = ("teapotF", "teapot", "mig16", "cfg3", "cfg5", "default")
 
 
@@ -74,6 +76,13 @@ class SceneDesc(C.Structure):
 class SceneInfo(C.Structure):
     _fields_ = [("num_prims", C.c_uint32), ("nodes_used", C.c_uint32), ("depth", C.c_uint32), ("max_leaf", C.c_uint32),
                 ("num_refs", C.c_uint32)]
+
+
+class BvhCost(C.Structure):
+    """rt_bvh_cost"""
+    _fields_ = [("sah", C.c_double), ("interior_area", C.c_double), ("leaf_area", C.c_double), ("leaf_cost", C.c_double),
+                ("root_area", C.c_double), ("interiors", C.c_uint32), ("leaves", C.c_uint32), ("refs", C.c_uint32),
+                ("max_leaf", C.c_uint32)]
 
 
 class Camera(C.Structure):
@@ -130,6 +139,11 @@ def lib():
         "rt_bvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, vp, C.POINTER(u32), C.POINTER(SceneInfo)],
                               C.c_int),
         "rt_bvh_refit_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, vp, u32, C.POINTER(u32)], C.c_int),
+        "rt_bvh_cost_host": ([vp, u32, C.POINTER(BvhCost)], C.c_int),
+        "rt_bvh_visualize_nodes": ([vp, u32, vp, vp, u32], C.c_int),
+        "rt_bvh_visualize": ([vp, vp, vp, u32, vp], C.c_int),
+        "rt_bvh_visualize_host": ([vp, vp, vp, u32], C.c_int),
+        "rt_scene_bvh_cost": ([vp, C.POINTER(BvhCost), vp], C.c_int),
         "rt_scene_update_triangles": ([vp, u32, u32, vp, vp], C.c_int),
         "rt_scene_update_triangles_host": ([vp, u32, u32, fp], C.c_int),
         "rt_scene_update_prims": ([vp, u32, u32, vp, vp, vp], C.c_int),
@@ -362,6 +376,31 @@ def build_sbvh_host(prims):
         L.rt_free(nodes)
         L.rt_free(C.cast(idx, C.c_void_p))
     return out_nodes, out_idx, _info_dict(info)
+
+
+def _cost_dict(c):
+    return {n: (float if t is C.c_double else int)(getattr(c, n)) for n, t in BvhCost._fields_}
+
+
+def bvh_visualize_nodes(nodes, rays):
+    """rt_bvh_visualize_nodes: Scene::BVHVisualization on the host over a BVHNode array (nodes [n, 32]
+    uint8 as build_bvh_host / Scene.bvh return them) -- uint32 [len(rays), 2]: nodes visited, leaves
+    reached per ray (rays [n, 7]: O, D, tmax)."""
+    N = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 32)
+    R = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+    out = np.zeros((len(R), 2), np.uint32)
+    _check(lib().rt_bvh_visualize_nodes(N.ctypes.data_as(C.c_void_p), len(N), R.ctypes.data_as(C.c_void_p),
+                                        out.ctypes.data_as(C.c_void_p), len(R)))
+    return out
+
+
+def bvh_cost_host(nodes):
+    """rt_bvh_cost_host: the tree cost of a BVHNode array (nodes [n, 32] uint8) as a dict -- sah,
+    interior_area, leaf_area, leaf_cost, root_area, interiors, leaves, refs, max_leaf."""
+    N = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 32)
+    c = BvhCost()
+    _check(lib().rt_bvh_cost_host(N.ctypes.data_as(C.c_void_p), len(N), C.byref(c)))
+    return _cost_dict(c)
 
 
 def _info_dict(info):
@@ -643,6 +682,33 @@ class Scene:
             _check(self.L.rt_intersect(self.h, C.c_void_p(r.data_ptr()), C.c_void_p(hits.data_ptr()), n, C.c_void_p(s)))
         return hits[:, 0], hits.view(torch.int32)[:, 1], hits[:, 2], hits[:, 3]
 
+    def BVHVisualization(self, rays, stream=None):
+        """Batched Scene::BVHVisualization (template/scene.h:244-283).  rays: (n, 7) [O, D, tmax] numpy or
+        torch.  Returns a torch int32 [n, 2] on the scene's device: nodes visited, leaves reached."""
+        torch = _torch()
+        r = _as_device_rays(rays, self.device)
+        n = r.shape[0]
+        out = torch.empty((n, 2), dtype=torch.int32, device=r.device)
+        s = stream if stream is not None else torch.cuda.current_stream(r.device).cuda_stream
+        _check(self.L.rt_bvh_visualize(self.h, C.c_void_p(r.data_ptr()) if n else None,
+                                       C.c_void_p(out.data_ptr()) if n else None, n, C.c_void_p(s)))
+        return out
+
+    def bvh_visualize_host(self, rays):
+        """Host-array variant of BVHVisualization: uint32 [n, 2]."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 7)
+        out = np.zeros((len(rays), 2), np.uint32)
+        _check(self.L.rt_bvh_visualize_host(self.h, rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                            len(rays)))
+        return out
+
+    def bvh_cost(self, stream=None):
+        """rt_scene_bvh_cost: the cost of the scene's current device tree, reduced on the GPU, as the dict
+        of bvh_cost_host.  Compare sah after a refit with its value after the last rebuild."""
+        c = BvhCost()
+        _check(self.L.rt_scene_bvh_cost(self.h, C.byref(c), C.c_void_p(stream)))
+        return _cost_dict(c)
+
     def set_camera_walk(self, walk):
         """WALK_LANE, WALK_WAVE or WALK_AUTO (default): how camera rays walk the BVH (same results)."""
         _check(self.L.rt_scene_set_camera_walk(self.h, walk))
@@ -736,7 +802,8 @@ class Renderer:
         self.h = C.c_void_p()
         _check(self.L.rt_renderer_create(scene.h, width, height, C.byref(self.h)))
         self.frame = 0
-        self.mode = MODE_PATH     # MODE_PATH / MODE_WHITTED / MODE_PACKET (the PACKET_TRAVERSAL build)
+        self.mode = MODE_PATH     # MODE_PATH / MODE_WHITTED / MODE_PACKET (the PACKET_TRAVERSAL build) /
+                                  # MODE_BVH_HEAT (the BVH_ANALYSIS build)
 
     @property
     def useWhitted(self):       # renderer.h:158; toggled by the K key (renderer.h:138)

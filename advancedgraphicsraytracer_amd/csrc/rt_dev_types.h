@@ -172,6 +172,12 @@ struct TraceArgs {
 RT_DECLARE_LAUNCHERS(kcore)
 RT_DECLARE_LAUNCHERS(kext)
 #undef RT_DECLARE_LAUNCHERS
+// BVH analysis (RT_MODE_BVH_HEAT frames, rt_bvh_visualize): node reads only, so the core build
+// carries it for every scene.  launch_heat: F.depth = the tree's depth, plain tile order.
+namespace kcore {
+void launch_heat(const SceneView &S, const FrameArgs &F, size_t lds, hipStream_t st);
+void launch_visualize(const SceneView &S, const rt_ray *rays, uint32_t *counts, uint32_t n, size_t lds, hipStream_t st);
+}
 // where: per global tile (shard << 24 | local tile) of an explicit deal; nullptr = interleaved.
 // first = 1: `gathered` holds shards 1.. only (rank 0's own tiles are already in `out`)
 void launch_assemble(const uint32_t *gathered, uint32_t cap, uint32_t nshards, const uint32_t *where, uint32_t tiles_x,

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_cost.h"
 #include "rt_dev_types.h"
 #include "rt_internal.h"
 #include "rt_records.h"
@@ -101,6 +102,7 @@ struct rt_scene {
     void *d_nodes = nullptr, *d_prims = nullptr, *d_shade = nullptr, *d_mats = nullptr, *d_sky = nullptr;
     void *d_xprims = nullptr, *d_tex = nullptr;
     void *d_scratch = nullptr;  // staging for the host-pointer batched calls
+    void *d_cost = nullptr;     // rt_scene_bvh_cost's partial sums (rt_cost.hip), allocated by its first call
     size_t scratch_bytes = 0;
     hipStream_t stream = nullptr;
     RefitState refit;           // in-place updates (rt_refit.h)
@@ -233,7 +235,7 @@ void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads};
+    void *ptrs[] = {s->d_nodes, s->d_prims, s->d_shade, s->d_mats, s->d_sky, s->d_xprims, s->d_tex, s->d_scratch, s->d_quads, s->d_cost};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     free_refit(s->refit);
@@ -951,7 +953,7 @@ int frame_args(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
     if (p->width != r->W || p->height != r->H)
         return fail(RT_ERR_INVALID, "frame size differs from the renderer's accumulator");
     if (p->spp == 0) return fail(RT_ERR_INVALID, "spp must be >= 1");
-    if (p->mode > RT_MODE_PACKET) return fail(RT_ERR_INVALID, "unknown integrator mode");
+    if (p->mode > RT_MODE_BVH_HEAT) return fail(RT_ERR_INVALID, "unknown integrator mode");
     if (nshards == 0 || shard >= nshards) return fail(RT_ERR_INVALID, "bad shard index");
     HIP_TRY(hipSetDevice(r->scene->device));
     F = FrameArgs{};
@@ -1266,6 +1268,18 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     F.fwd_dst = fwd_dst;
     if (F.ntiles_local == 0) return RT_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (p->mode == RT_MODE_BVH_HEAT) {
+        // The BVH heat map: the plain serial launch in the tiles' own order.  It reads none of the
+        // renderer's timed choices and writes none (no parameter key, gate, walk, order or overlap
+        // step), so PATH frames before and after it see the state they left.  p->depth is ignored:
+        // the kernel's depth is the tree's (bvhDepth, template/scene.h:282).
+        F.depth = s->bvh.depth;
+        kcore::launch_heat(s->view, F, stack_bytes(s), st);
+        HIP_TRY(hipGetLastError());
+        r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
+        r->frames += 1;
+        return RT_OK;
+    }
     if (p->depth > 32) return fail(RT_ERR_UNSUPPORTED, "Trace depth above 32");   // = kWHITTED_MAX
     const int md = max_depth_class(p->depth);
     const bool tex = !s->view.sky_const;
@@ -1851,7 +1865,7 @@ int rt_trace_host(rt_scene *s, int mode, const rt_ray *rays, uint32_t *seeds, co
     return RT_OK;
 }
 
-enum { CALL_INTERSECT, CALL_OCCLUDED, CALL_PACKETS };
+enum { CALL_INTERSECT, CALL_OCCLUDED, CALL_PACKETS, CALL_VISUALIZE };
 static int staged_call(rt_scene *s, const rt_ray *rays, void *out, size_t out_elem, uint32_t n, int kind) {
     if (!s || (n && (!rays || !out))) return fail(RT_ERR_INVALID, "null argument");
     if (n == 0) return RT_OK;
@@ -1863,6 +1877,7 @@ static int staged_call(rt_scene *s, const rt_ray *rays, void *out, size_t out_el
     HIP_TRY(hipMemcpyAsync(d_rays, rays, sizeof(rt_ray) * n, hipMemcpyHostToDevice, s->stream));
     int rc = kind == CALL_OCCLUDED ? rt_occluded(s, d_rays, (uint8_t *)d_out, n, s->stream)
              : kind == CALL_PACKETS ? rt_intersect_packets(s, d_rays, (rt_hit *)d_out, n, s->stream)
+             : kind == CALL_VISUALIZE ? rt_bvh_visualize(s, d_rays, (uint32_t *)d_out, n, s->stream)
                                     : rt_intersect(s, d_rays, (rt_hit *)d_out, n, s->stream);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out, out_elem * n, hipMemcpyDeviceToHost, s->stream));
@@ -1878,6 +1893,30 @@ int rt_occluded_host(rt_scene *s, const rt_ray *rays, uint8_t *out, uint32_t n) 
 }
 int rt_intersect_packets_host(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n) {
     return staged_call(s, rays, hits, sizeof(rt_hit), n, CALL_PACKETS);
+}
+
+// Batched Scene::BVHVisualization (k_bvh_visualize; the core build serves every scene: nodes only)
+int rt_bvh_visualize(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t n, void *stream) {
+    if (!s || (n && (!rays || !counts))) return fail(RT_ERR_INVALID, "rt_bvh_visualize: null argument");
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    kcore::launch_visualize(s->view, rays, counts, n, stack_bytes(s), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+int rt_bvh_visualize_host(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t n) {
+    return staged_call(s, rays, counts, 2 * sizeof(uint32_t), n, CALL_VISUALIZE);
+}
+
+// Tree cost of the scene's current device nodes (rt_cost.hip)
+int rt_scene_bvh_cost(rt_scene *s, rt_bvh_cost *out, void *stream) {
+    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_bvh_cost: null argument");
+    if (!s->view.bounds_finite) return fail(RT_ERR_UNSUPPORTED, "rt_scene_bvh_cost: a node bound is NaN or infinite");
+    HIP_TRY(hipSetDevice(s->device));
+    rt_bvh_cost c{};
+    const int rc = device_bvh_cost(s->d_nodes, s->bvh.nodes_used, &s->d_cost, (hipStream_t)stream, &c);
+    if (rc == RT_OK) *out = c;
+    return rc;
 }
 
 int rt_renderer_create(rt_scene *s, uint32_t W, uint32_t H, rt_renderer **out) {
@@ -2155,6 +2194,7 @@ int rt_renderer_read_accumulator(rt_renderer *r, float *host) {
 }
 
 const char *rt_frame_kernel_name(const rt_renderer *r, const rt_frame_params *p) {
+    if (r && p && p->mode == RT_MODE_BVH_HEAT) return "k_render_heat";   // its depth is the tree's
     if (!r || !p || p->mode > RT_MODE_PACKET || p->depth > 32) {
         fail(RT_ERR_INVALID, "rt_frame_kernel_name: bad argument");
         return nullptr;

@@ -24,6 +24,7 @@
 
 #include <zlib.h>
 
+#include "rt_cost.h"
 #include "rt_internal.h"
 #include "rt_records.h"
 
@@ -946,6 +947,79 @@ int rt_bvh_refit_host(const rt_prim *prims, const float *transforms, uint32_t n,
     } catch (const std::exception &e) {
         return fail(RT_ERR_INVALID, std::string("rt_bvh_refit_host: ") + e.what());
     }
+}
+
+// Scene::BVHVisualization (template/scene.h:244-283) on the host, the twin of k_bvh_visualize: the
+// walk of IntersectBVH without the primitive tests, so the ray's t never shrinks.  The tree is checked
+// once (child pairs inside the array, no leaf deeper than the 64-entry stack) before any ray walks it.
+int rt_bvh_visualize_nodes(const void *nodes, uint32_t nodes_used, const rt_ray *rays, uint32_t *counts, uint32_t n) {
+    if (!nodes || nodes_used == 0 || (n && (!rays || !counts))) return fail(RT_ERR_INVALID, "rt_bvh_visualize_nodes: null or empty argument");
+    try {
+        std::vector<Node> N(nodes_used);
+        std::memcpy(N.data(), nodes, sizeof(Node) * nodes_used);
+        TreeWalk w;
+        switch (walk_tree(N.data(), nodes_used, ~(size_t)0, w)) {
+        case kTreeCycle: return fail(RT_ERR_INVALID, "rt_bvh_visualize_nodes: the tree has a cycle");
+        case kTreeChildRange: return fail(RT_ERR_INVALID, "rt_bvh_visualize_nodes: child pair out of range");
+        }
+        for (uint32_t k : w.order)
+            if (w.depth[k] > 64) return fail(RT_ERR_INVALID, "rt_bvh_visualize_nodes: tree deeper than 64 (the reference's stack[64])");
+        auto dist = [](const Node &b, f3 O, f3 rD, float t) {   // IntersectAABB, template/scene.h:432-450
+            const float tx1 = (b.mn[0] - O.x) * rD.x, tx2 = (b.mx[0] - O.x) * rD.x;
+            float tmn = smin(tx1, tx2), tmx = smax(tx1, tx2);
+            const float ty1 = (b.mn[1] - O.y) * rD.y, ty2 = (b.mx[1] - O.y) * rD.y;
+            tmn = smax(tmn, smin(ty1, ty2)); tmx = smin(tmx, smax(ty1, ty2));
+            const float tz1 = (b.mn[2] - O.z) * rD.z, tz2 = (b.mx[2] - O.z) * rD.z;
+            tmn = smax(tmn, smin(tz1, tz2)); tmx = smin(tmx, smax(tz1, tz2));
+            return (tmx >= tmn && tmn < t && tmx > 0) ? tmn : 1e30f;
+        };
+        for (uint32_t i = 0; i < n; ++i) {
+            const rt_ray &q = rays[i];
+            const f3 O = mk(q.ox, q.oy, q.oz), rD = mk(1 / q.dx, 1 / q.dy, 1 / q.dz);
+            uint32_t stack[64], sp = 0, k = 0, visits = 0, leaves = 0;
+            for (;;) {
+                ++visits;
+                const Node &nd = N[k];
+                if (nd.count > 0) {
+                    ++leaves;
+                    if (sp == 0) break;
+                    k = stack[--sp];
+                    continue;
+                }
+                uint32_t c1 = nd.leftFirst, c2 = nd.leftFirst + 1;
+                float d1 = dist(N[c1], O, rD, q.tmax), d2 = dist(N[c2], O, rD, q.tmax);
+                if (d1 > d2) { std::swap(d1, d2); std::swap(c1, c2); }
+                if (d1 == 1e30f) {
+                    if (sp == 0) break;
+                    k = stack[--sp];
+                } else {
+                    k = c1;
+                    if (d2 != 1e30f) stack[sp++] = c2;
+                }
+            }
+            counts[2 * (size_t)i] = visits;
+            counts[2 * (size_t)i + 1] = leaves;
+        }
+        return RT_OK;
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_bvh_visualize_nodes: ") + e.what());
+    }
+}
+
+int rt_bvh_cost_host(const void *nodes, uint32_t nodes_used, rt_bvh_cost *out) {
+    if (!nodes || !out || nodes_used == 0) return fail(RT_ERR_INVALID, "rt_bvh_cost_host: null or empty argument");
+    const Node *N = static_cast<const Node *>(nodes);
+    CostPart c{};
+    for (uint32_t i = 0; i < nodes_used; ++i) {
+        if (i == 1u) continue;   // the reference's unused node
+        Node nd;
+        std::memcpy(&nd, N + i, sizeof(Node));
+        cost_add(c, mk(nd.mn[0], nd.mn[1], nd.mn[2]), mk(nd.mx[0], nd.mx[1], nd.mx[2]), nd.count);
+    }
+    Node root;
+    std::memcpy(&root, N, sizeof(Node));
+    cost_finish(c, box_area(mk(root.mn[0], root.mn[1], root.mn[2]), mk(root.mx[0], root.mx[1], root.mx[2])), out);
+    return RT_OK;
 }
 
 int rt_sbvh_build_host(const rt_prim *prims, const float *transforms, uint32_t n, void **nodes, uint32_t **indices,

@@ -1551,6 +1551,105 @@ __global__ __launch_bounds__(256) void k_occluded(SceneView S, const rt_ray *__r
     out[i] = occluded(S, T, r) ? 1 : 0;
 }
 
+#if RT_EXT == 0
+// ------------------------------------------------------------------ BVH analysis (scene.h:244-283)
+// Scene::BVHVisualization: the walk of closest_hit_t with leaf_closest taken out, so r.t never
+// shrinks -- nearer child first, the farther one pushed when its distance is not 1e30f; the root's
+// own box is never tested.  visits counts every node met (interior or leaf), leaves the leaves; both
+// live in registers.  It reads nodes only (no primitive, shading or material record), which is why
+// it is compiled into the core build alone: the host launches that build for every scene (the node
+// array, root word and stack depth mean the same to both builds).  The stack needs what
+// closest_hit_t's needs: an entry per interior ancestor.
+template <bool FAST, class TR>
+__device__ __forceinline__ void heat_walk_t(const SceneView &S, const TR &T, const DRay &r, uint32_t &visits,
+                                            uint32_t &leaves) {
+    uint32_t word = S.root_word;
+    int sp = 0;
+    for (;;) {
+        ++visits;
+        if (word & 0xffu) {
+            ++leaves;
+            if (sp == 0) return;
+            word = stack_pop(T, sp);
+            continue;
+        }
+        float n1, x1, n2, x2;
+        uint32_t w1, w2;
+        child_pair<FAST>(T, r, word >> 8, n1, x1, n2, x2, w1, w2);
+        const float e1 = slab_accept(r, n1, x1), e2 = slab_accept(r, n2, x2);
+        const bool sw = e1 > e2;
+        const float d1 = sw ? e2 : e1, d2 = sw ? e1 : e2;
+        if (d1 == 1e30f) {
+            if (sp == 0) return;
+            word = stack_pop(T, sp);
+        } else {
+            word = sw ? w2 : w1;
+            if (d2 != 1e30f) stack_push(T, sp, sw ? w1 : w2);
+        }
+    }
+}
+template <class TR>
+__device__ __forceinline__ void heat_walk(const SceneView &S, const TR &T, const DRay &r, uint32_t &visits,
+                                          uint32_t &leaves) {
+    if (__all(S.bounds_finite && ray_finite(r))) heat_walk_t<true>(S, T, r, visits, leaves);
+    else heat_walk_t<false>(S, T, r, visits, leaves);
+}
+
+// The RT_MODE_BVH_HEAT frame (the BVH_ANALYSIS build of Tick, renderer.cpp:224-226): k_render's launch
+// shape -- one wave per 8x8 tile, the tiles in their plain order (no measured order, no sample split,
+// no stored samples) -- with BVHVisualization's colour as the sample's value, then render_tile's
+// accumulate / pack / store.  F.depth holds the TREE's depth (bvhDepth), not a Trace depth.
+__global__ __launch_bounds__(256) void k_render_heat(SceneView S, FrameArgs F) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t local_tile = blockIdx.x * 4u + (tid >> 6);
+    if (local_tile >= F.ntiles_local) return;
+    Trav<256> T{S.nodes, lds_stack + tid, S.prims};
+    const uint32_t tile = global_tile(F, local_tile);
+    const uint32_t x = (tile % F.tiles_x) * 8u + (lane & 7u), y = (tile / F.tiles_x) * 8u + (lane >> 3);
+    if (!(x < F.W && y < F.H)) return;
+    const uint32_t px = x + y * F.W;
+    const float depth = (float)F.depth;
+    f3 sum = mk(0, 0, 0);
+    for (uint32_t s = 0; s < F.spp; ++s) {
+        uint32_t seed = init_seed(px + F.W * F.H * (s + F.spp * F.frame));
+        const DRay ray = primary_ray(F, x, y, seed);
+        uint32_t visits = 0, leaves = 0;
+        heat_walk(S, T, ray, visits, leaves);
+        sum = sum + mk((float)leaves / depth, (0.25f * (float)visits) / depth, 0.0f);   // scene.h:282
+    }
+    f3 res = (1.0f / (float)F.spp) * sum;
+    float4 a = F.reset ? make_float4(0, 0, 0, 0) : F.acc[px];
+    a.w += 1;                                                          // renderer.cpp:237-240
+    const float w = a.w, inv = 1.0f / w;
+    a = make_float4(a.x + inv * (res.x - a.x), a.y + inv * (res.y - a.y), a.z + inv * (res.z - a.z),
+                    a.w + inv * (w - a.w));
+    F.acc[px] = a;
+    const uint32_t rgb = pack_rgb8(a);
+    if (F.packed_out) F.out[local_tile * 64u + lane] = rgb;
+    else {
+        if (F.fwd_dst) F.fwd_dst[px] = F.fwd_src[px];
+        F.out[px] = rgb;
+    }
+}
+
+// batched BVHVisualization on caller rays (rt_bvh_visualize): one lane per ray, counts[2i] = nodes
+// visited, counts[2i + 1] = leaves reached
+__global__ __launch_bounds__(256) void k_bvh_visualize(SceneView S, const rt_ray *__restrict__ rays,
+                                                       uint32_t *__restrict__ counts, uint32_t n) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    rt_ray q = rays[i];
+    const DRay r = make_ray(mk(q.ox, q.oy, q.oz), mk(q.dx, q.dy, q.dz), q.tmax);
+    Trav<256> T{S.nodes, lds_stack + threadIdx.x, S.prims};
+    uint32_t visits = 0, leaves = 0;
+    heat_walk(S, T, r, visits, leaves);
+    counts[2 * (size_t)i] = visits;
+    counts[2 * (size_t)i + 1] = leaves;
+}
+#endif
+
 // Batched Renderer::Trace(ray, lastSpecular, depth) (renderer.cpp:17-72) / WhittedTrace(ray,
 // depth) (renderer.cpp:138-195): one lane per caller ray, the ray's own RNG state in and out.
 // The optional hit record is the ray as the first IntersectBVH leaves it (renderer.cpp:20),
@@ -2379,6 +2478,14 @@ void launch_occluded(const SceneView &S, const rt_ray *rays, uint8_t *out, uint3
 void launch_intersect_packet(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_intersect_packet, dim3((n + 255) / 256), dim3(256), 0, st, S, rays, hits, n);
 }
+#if RT_EXT == 0
+void launch_heat(const SceneView &S, const FrameArgs &F, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_render_heat, dim3((F.ntiles_local + 3u) / 4u), dim3(256), lds, st, S, F);
+}
+void launch_visualize(const SceneView &S, const rt_ray *rays, uint32_t *counts, uint32_t n, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_bvh_visualize, dim3((n + 255) / 256), dim3(256), lds, st, S, rays, counts, n);
+}
+#endif
 
 }  // namespace RT_KNS
 

@@ -757,6 +757,9 @@ int rt_render_frame_multi(rt_renderer *r, rt_comm *c, const rt_camera *cam, cons
     if (!r || !c || !cam || !p) return fail(RT_ERR_INVALID, "rt_render_frame_multi: null argument");
     if (flags & ~(uint32_t)(RT_MULTI_PIPELINED | RT_MULTI_TIMING | RT_MULTI_BALANCED))
         return fail(RT_ERR_INVALID, "rt_render_frame_multi: unknown flags");
+    // every rank passes the same params, so every rank refuses alike, before any collective
+    if (p->mode == RT_MODE_BVH_HEAT)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_frame_multi: RT_MODE_BVH_HEAT frames are single-GPU (rt_render_frame, rt_render_shard)");
     const bool pipelined = (flags & RT_MULTI_PIPELINED) != 0;
     // every check before the first side effect: a rejected call leaves the accumulator, the
     // frame count and the communicator as they were

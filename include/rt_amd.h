@@ -56,8 +56,14 @@ enum { RT_DIFFUSE = 0, RT_MIRROR = 1, RT_DIELECTRIC = 2, RT_CHECKERBOARD = 3, RT
  * (default depth 20, renderer.h:13), and the PACKET_TRAVERSAL build of Tick
  * (renderer.cpp:247-285): 8x8 tiles as 64-ray packets through IntersectBVHPacket, shaded
  * by TracePacket whose bounces are Trace(.., depth) -- depth 10 in the reference, 0 allowed.
- * depth <= 32 for all three. */
-enum { RT_MODE_PATH = 0, RT_MODE_WHITTED = 1, RT_MODE_PACKET = 2 };
+ * depth <= 32 for all three.
+ * RT_MODE_BVH_HEAT: the BVH_ANALYSIS build of Tick (renderer.cpp:224-226) -- every sample is
+ * Scene::BVHVisualization (template/scene.h:244-283) of its camera ray instead of Trace: red =
+ * leaves reached / tree depth, green = 0.25 * nodes visited / tree depth, blue = 0, through the same
+ * accumulator and RGB8 pack.  rt_frame_params.depth is ignored; no shadow or bounce ray is counted.
+ * Frames only (rt_render_frame, _host, rt_render_shard, rt_render_shard_tiles); rt_render_frame_multi
+ * refuses it with RT_ERR_UNSUPPORTED. */
+enum { RT_MODE_PATH = 0, RT_MODE_WHITTED = 1, RT_MODE_PACKET = 2, RT_MODE_BVH_HEAT = 3 };
 
 /* One primitive, Primitive::create* factories (Primitive.h:690-747):
  *   RT_SPHERE:   v[0..2] centre, v[3] radius
@@ -166,6 +172,20 @@ int rt_bvh_build_host(const rt_prim *prims, const float *transforms, uint32_t n,
  * exactly one leaf): RT_ERR_UNSUPPORTED for an SBVH's index array; the nodes are untouched on error. */
 int rt_bvh_refit_host(const rt_prim *prims, const float *transforms, uint32_t n, void *nodes, uint32_t nodes_used,
                       const uint32_t *indices);
+/* Tree cost, the per-node SAH term of calculateNodeCost (template/scene.h:203-207) summed over a tree.
+ * Over every node index in [0, nodes_used) except 1 (the reference's unused node), from the float32
+ * bounds: ex = (double)max.x - (double)min.x (ey, ez alike), area = ex*ey + ey*ez + ez*ex, left to
+ * right in double without contraction (a plane's +-1e30 box overflows float32).  An interior node adds
+ * area to interior_area; a leaf adds area to leaf_area and (double)count * area to leaf_cost; refs =
+ * the sum of the leaf counts, max_leaf the largest; root_area = node 0's area.  The order of the
+ * double sums is free. */
+typedef struct {
+    double sah;            /* (interior_area + leaf_cost) / root_area; 0 when root_area == 0 */
+    double interior_area, leaf_area, leaf_cost, root_area;
+    uint32_t interiors, leaves, refs, max_leaf;
+} rt_bvh_cost;
+/* no device: the cost of a BVHNode array (rt_bvh_build_host's, rt_scene_copy_bvh's) */
+int rt_bvh_cost_host(const void *nodes, uint32_t nodes_used, rt_bvh_cost *out);
 /* the opt-in spatial-split BVH (RT_BVH_SBVH) on the host: library-allocated nodes
  * (info->nodes_used x 32 B) and primitive-index array (info->num_refs; primitives may
  * repeat); free both with rt_free */
@@ -308,6 +328,14 @@ int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, cons
                               void *stream);
 /* the same with the records in host memory (staged on the scene's private stream) */
 int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert);
+/* rt_bvh_cost of the scene's CURRENT device tree -- the node records as they are after any number of
+ * updates, rebuilds and splices -- reduced on the GPU (per workgroup, then over the workgroups' partial
+ * sums; no copy of the tree to the host).  Blocks like rt_renderer_tile_work: runs on `stream` and
+ * returns with *out filled.  "Refit or rebuild?": compare sah after a refit with its value after the
+ * last rebuild.
+ *   RT_ERR_INVALID      null argument;
+ *   RT_ERR_UNSUPPORTED  a scene whose node bounds are not all finite -- *out is untouched. */
+int rt_scene_bvh_cost(rt_scene *s, rt_bvh_cost *out, void *stream);
 
 /* Batched Scene::IntersectBVH (template/scene.h:285-320): rays_dev[n] -> hits_dev[n]. */
 int rt_intersect(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, uint32_t n, void *stream);
@@ -321,6 +349,16 @@ int rt_intersect_packets(rt_scene *s, const rt_ray *rays_dev, rt_hit *hits_dev, 
 int rt_intersect_host(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n);
 int rt_occluded_host(rt_scene *s, const rt_ray *rays, uint8_t *out, uint32_t n);
 int rt_intersect_packets_host(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n);
+/* Batched Scene::BVHVisualization (template/scene.h:244-283): counts_dev[2i] = nodeTraversals,
+ * counts_dev[2i+1] = intersections (leaves reached) of rays_dev[i]; the ray's tmax is its t.  The walk
+ * is IntersectBVH's with the primitive tests taken out, so t never shrinks; the root's own box is
+ * never tested (a root that is a leaf gives (1, 1) for every ray). */
+int rt_bvh_visualize(rt_scene *s, const rt_ray *rays_dev, uint32_t *counts_dev, uint32_t n, void *stream);
+int rt_bvh_visualize_host(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t n);
+/* no device: the same walk over a BVHNode array (rt_bvh_build_host's, rt_scene_copy_bvh's).
+ * RT_ERR_INVALID for a null pointer, a tree deeper than 64 or a child index outside nodes_used --
+ * nothing is written then. */
+int rt_bvh_visualize_nodes(const void *nodes, uint32_t nodes_used, const rt_ray *rays, uint32_t *counts, uint32_t n);
 
 /* Batched Renderer::Trace(Ray&, bool lastSpecular, int depth) (renderer.h:9, renderer.cpp:17-72)
  * or, with mode RT_MODE_WHITTED, Renderer::WhittedTrace(Ray&, int depth) (renderer.h:13,
@@ -500,7 +538,8 @@ int rt_renderer_walk_stats(rt_renderer *r, uint64_t out[4]);
 /* accumulator readback, W*H float4 */
 int rt_renderer_read_accumulator(rt_renderer *r, float *host_out);
 /* Name of the frame kernel rt_render_frame / rt_render_shard launch for these params
- * (as it appears in rocprofv3 kernel traces, template arguments abbreviated); for
+ * (as it appears in rocprofv3 kernel traces, template arguments abbreviated; "k_render_heat" for
+ * RT_MODE_BVH_HEAT); for
  * profiling and the bench's roofline line.  NULL on a bad argument. */
 const char *rt_frame_kernel_name(const rt_renderer *r, const rt_frame_params *p);
 int rt_renderer_stream(rt_renderer *r, void **stream);

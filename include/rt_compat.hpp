@@ -292,6 +292,13 @@ class Scene {   // template/scene.h:37
     // Scene::BuildBVH (template/scene.h:845): the tree of the current primitives, rebuilt on the GPU after
     // in-place updates have moved them; the next Tick resets the accumulator
     void BuildBVH(void *stream = nullptr) { rt_check(rt_scene_rebuild(handle(), stream)); }
+    // calculateNodeCost (template/scene.h:203-207) summed over the current device tree, on the GPU:
+    // compare .sah after in-place updates with its value after the last BuildBVH
+    rt_bvh_cost BVHCost(void *stream = nullptr) {
+        rt_bvh_cost c{};
+        rt_check(rt_scene_bvh_cost(handle(), &c, stream));
+        return c;
+    }
     // A mesh enters or leaves, or is swapped for one of another size, without a new Scene: triangle
     // primitives [first, first + remove) go, `insert` new ones (rt_prim records in host memory) come in at
     // id `first`, and the tree is rebuilt on the GPU.  Ids behind the edit shift by insert - remove; the
@@ -378,7 +385,7 @@ class Renderer : public TheApp {   // renderer.h:5-160
     void Tick(float /*deltaTime*/, uint32_t depth, uint32_t spp = 1) {
         if (!h_) Init();
         if (depth == 0) depth = useWhitted ? 20 : 10;
-        const uint32_t mode = useWhitted ? RT_MODE_WHITTED : usePackets ? RT_MODE_PACKET : RT_MODE_PATH;
+        const uint32_t mode = bvhAnalysis ? RT_MODE_BVH_HEAT : useWhitted ? RT_MODE_WHITTED : usePackets ? RT_MODE_PACKET : RT_MODE_PATH;
         rt_frame_params p{width_, height_, spp, depth, frame_++, mode, tracerSwap ? 1u : 0u};
         tracerSwap = false;
         uint32_t *out = pixels.data();
@@ -479,6 +486,8 @@ class Renderer : public TheApp {   // renderer.h:5-160
     bool useWhitted = false;        // renderer.h:158
     bool tracerSwap = false;        // renderer.h:159: the next frame restarts accumulation
     bool usePackets = false;        // PACKET_TRAVERSAL, Ray.h:3
+    bool bvhAnalysis = false;       // BVH_ANALYSIS (renderer.cpp:224-226): Scene::BVHVisualization per sample;
+                                    // set tracerSwap when it changes
     std::vector<uint32_t> pixels;   // 0x00RRGGBB, the frame when no screen Surface is attached
 };
 
