@@ -3,9 +3,10 @@
 //
 // One text for gfx950 and for the host, like rt_update.h and under the same -ffp-contract=off.  The
 // kernels of rt_build.hip supply a *lane context* P -- the lane index and count (tid, stride), the
-// workgroup barrier (bar) and integer atomics (amax, aadd) -- and a stand-alone host program runs the
-// same steps in the same order with SerialLane: tid = 0, stride = 1, no barrier, plain stores
-// (tests/cpp/build_host.cpp).  No std:: algorithm.
+// workgroup barrier (bar) and integer atomics (amax, aadd) -- and the stand-alone host programs run the
+// same steps with SerialLane: tid = 0, stride = 1, no barrier, plain stores.  The order of the steps
+// (build_order) and the sizes of the arrays (build_carve) are here too, once for both: the device
+// supplies an executor that launches, the host one that loops (tests/cpp/host_build.h).  No std:: algorithm.
 //
 // Why many lanes reproduce the sequential builder bit for bit: every *decision* is order-independent.
 // Node and bin boxes and the centroid bounds are min / max, here integer atomic max over
@@ -581,6 +582,115 @@ RT_HD void box_level(const BuildArgs &B, uint32_t nodes_used, uint32_t d, uint32
     A.margin = B.margin;
     for (uint32_t k = gtid; k < nodes_used; k += gstride)
         if (B.depth_of[k] == d) refit_node(A, k);
+}
+
+// ---- the array sizes, in elements: the work arrays (A: anything with take<T>(count) -- the device
+// carves one allocation, the host programs give every array a heap block of its own) and the outputs
+template <class A>
+void build_carve(A &a, uint32_t n, BuildArgs &B) {
+    B.idx2 = a.template take<uint32_t>(n);
+    B.ptab = a.template take<uint32_t>(n);
+    B.qtab = a.template take<uint32_t>(n);
+    B.rk = a.template take<uint32_t>(n);
+    B.node = a.template take<BNode>(2 * (size_t)n + 2);
+    B.bflag = a.template take<uint32_t>((size_t)n + 1);
+    B.csum = a.template take<uint32_t>(scan_runs(n) + 1u);
+    B.ctr = a.template take<uint32_t>(kCtrWords);
+    B.wacc = a.template take<uint32_t>((size_t)build_wide_cap(n) * kAccWords);
+    for (int k = 0; k < 2; ++k) {
+        B.wnode[k] = a.template take<WNode>(build_wide_cap(n));
+        B.task[k] = a.template take<BTask>(build_task_cap(n));
+    }
+    B.chunkL = a.template take<uint32_t>(build_task_cap(n));
+    B.slist = a.template take<uint32_t>((size_t)n + 1);
+    B.depth_of = a.template take<uint32_t>(2 * (size_t)n + 2);
+}
+inline size_t build_nodes_len(uint32_t n) { return 2 * (2 * (size_t)n + 2); }   // float4: BuildArgs::nodes
+inline size_t build_prims_len(uint32_t n) { return 3 * (size_t)n; }             // float4: prims
+inline size_t build_slot_box_len(uint32_t n) { return 2 * (size_t)n; }          // float4: slot_box
+inline size_t build_ids_len(uint32_t n) { return n; }                           // uint32: slot_of, idx
+
+// ---- the launch order.  A step is one kernel of rt_build.hip, or on the host a loop over its workgroups:
+//   kStepInit                    the identity index array, the root
+//   per level of the many-workgroup path (nodes of more than kBuildWide primitives, a workgroup per
+//   kBuildChunk primitives):
+//     kStepWideBounds, -Bins         node box, centroid bounds, bins: LDS accumulators merged into the node's
+//     kStepWidePlane                 the plane, the cost abort, the chunk's left count
+//     kStepWideSettle                per node: the chunk counts' prefix, the children, the next level's tasks
+//     kStepWideTables, -Move, -Back  the partition
+//   kStepSubtrees                one workgroup per subtree of at most kBuildWide primitives, explicit stack
+//   kStepScanSum / -Top / -Apply the prefix count over the split boundaries that numbers the nodes
+//   kStepEmit                    node words in the host's numbering, depths, widest leaf
+//   kStepPermute                 leaf-slot records, slot boxes and the slot map in the new order
+//   kStepBoxes                   per depth, deepest first: stored boxes and sticky words (refit_node)
+// Nothing is handed from one workgroup to another inside a launch -- no flags, no spins, no fences
+// (the rule of rt_refit.hip): launch boundaries order the steps of a level and the levels, and
+// __syncthreads() orders the steps inside a workgroup, whose waves share their CU's vector L1.
+// The launches of the level loop are bounded by the depth limit: kBuildMaxDepth + 1 levels.
+enum BuildStep {
+    kStepInit, kStepWideBounds, kStepWideBins, kStepWidePlane, kStepWideSettle, kStepWideTables, kStepWideMove, kStepWideBack,
+    kStepSubtrees, kStepScanSum, kStepScanTop, kStepScanApply, kStepEmit, kStepPermute, kStepBoxes
+};
+// what build_order returns: kBuildOk, the executor's own failure, or the refusal
+enum { kBuildOk = 0, kBuildExec, kBuildLevels, kBuildTableOverrun, kBuildListOverrun, kBuildDeep, kBuildWideLeaf, kBuildNodes };
+struct BuildFigures { uint32_t nodes_used, depth, max_leaf, levels, wide_splits, subtrees, launches; };
+
+// The executor X runs the steps where the arrays live; each method returns false on a failure of its own:
+//   zero(ptr, words)          uint32 words to 0
+//   read(dst, src, words)     uint32 words of an array to the host, after every step before it
+//   step(BuildStep, count, arg)
+//       count: the lanes of a per-element step (Init, WideSettle, Scan*, Emit, Permute, Boxes), the
+//       workgroups of a per-workgroup step; arg: the level of a Wide step, the depth of Boxes
+// Plain C++: no HIP, no std:: algorithm.
+template <class X>
+int build_order(X &x, const BuildArgs &B, BuildFigures &f) {
+    const uint32_t n = B.n;
+    f = BuildFigures{};
+    if (!x.zero(B.ctr, kCtrWords) || !x.zero(B.bflag, (size_t)n + 1)) return kBuildExec;
+    if (!x.step(kStepInit, n, 0u)) return kBuildExec;
+    ++f.launches;
+    uint32_t lvl[2] = {0, 0};   // nodes and tasks of the level
+    if (!x.read(lvl, B.ctr + kCtrLevel, 2)) return kBuildExec;
+    for (uint32_t lv = 0; lvl[0] > 0; ++lv) {
+        if (lv > kBuildMaxDepth) return kBuildLevels;
+        if (lvl[0] > build_wide_cap(n) || lvl[1] > build_task_cap(n)) return kBuildTableOverrun;
+        if (!x.zero(B.wacc, kAccWords * (size_t)lvl[0])) return kBuildExec;
+        if (!x.step(kStepWideBounds, lvl[1], lv) || !x.step(kStepWideBins, lvl[1], lv) || !x.step(kStepWidePlane, lvl[1], lv) ||
+            !x.step(kStepWideSettle, lvl[0], lv) || !x.step(kStepWideTables, lvl[1], lv) || !x.step(kStepWideMove, lvl[1], lv) ||
+            !x.step(kStepWideBack, lvl[1], lv))
+            return kBuildExec;
+        f.launches += 7;
+        ++f.levels;
+        if (!x.read(lvl, B.ctr + kCtrLevel + 2u * (lv + 1u), 2)) return kBuildExec;
+    }
+    uint32_t ctr[kCtrLevel];
+    if (!x.read(ctr, B.ctr, kCtrLevel)) return kBuildExec;
+    f.subtrees = ctr[kCtrSmall];
+    if (f.subtrees > n) return kBuildListOverrun;
+    if (f.subtrees) {
+        if (!x.step(kStepSubtrees, f.subtrees, 0u)) return kBuildExec;
+        ++f.launches;
+    }
+    if (!x.step(kStepScanSum, scan_runs(n), 0u) || !x.step(kStepScanTop, 1u, 0u) || !x.step(kStepScanApply, scan_runs(n), 0u) ||
+        !x.step(kStepEmit, n, 0u))
+        return kBuildExec;
+    f.launches += 4;
+    if (!x.read(ctr, B.ctr, kCtrLevel)) return kBuildExec;
+    // take_tree's limits, before anything reads the new node words
+    f.nodes_used = 2u + 2u * ctr[kCtrSplits];
+    f.depth = ctr[kCtrDepth];
+    f.max_leaf = ctr[kCtrMaxLeaf];
+    f.wide_splits = ctr[kCtrWideSplit];
+    if ((ctr[kCtrErr] & kBuildErrDepth) || f.depth > kBuildMaxDepth) return kBuildDeep;
+    if (f.max_leaf > 255) return kBuildWideLeaf;
+    if (f.nodes_used > (1u << 24)) return kBuildNodes;
+    if (!x.step(kStepPermute, n, 0u)) return kBuildExec;
+    ++f.launches;
+    for (uint32_t d = f.depth + 1u; d-- > 0u;) {
+        if (!x.step(kStepBoxes, f.nodes_used, d)) return kBuildExec;
+        ++f.launches;
+    }
+    return kBuildOk;
 }
 
 }  // namespace rt

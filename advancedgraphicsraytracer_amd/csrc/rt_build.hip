@@ -1,24 +1,9 @@
 // rt_build.hip -- the GPU BVH rebuild: the kernels and the host path, rt::build_tree
 // over given inputs (rt::splice builds over a new id space with it) and rt::rebuild over the scene's own.
 //
-// rt_build.h holds every line a lane runs; the kernels here supply the lane context (lane index,
-// __syncthreads, integer atomics) and the launch order:
-//   k_init                       the identity index array, the root
-//   per level of the many-workgroup path (nodes of more than kBuildWide primitives, a workgroup per
-//   kBuildChunk primitives):
-//     k_wide_bounds, k_wide_bins     node box, centroid bounds, bins: LDS accumulators merged into the node's
-//     k_wide_plane                   the plane, the cost abort, the chunk's left count
-//     k_wide_settle                  per node: the chunk counts' prefix, the children, the next level's tasks
-//     k_wide_tables, k_wide_move, k_wide_back   the partition
-//   k_subtrees                   one workgroup per subtree of at most kBuildWide primitives, explicit stack
-//   k_scan_sum / _top / _apply   the prefix count over the split boundaries that numbers the nodes
-//   k_emit                       node words in the host's numbering, depths, widest leaf
-//   k_permute                    leaf-slot records, slot boxes and the slot map in the new order
-//   k_boxes                      per depth, deepest first: stored boxes and sticky words (refit_node)
-// Nothing is handed from one workgroup to another inside a launch -- no flags, no spins, no fences
-// (the rule of rt_refit.hip): launch boundaries order the steps of a level and the levels, and
-// __syncthreads() orders the steps inside a workgroup, whose waves share their CU's vector L1.
-// The launches of the level loop are bounded by the depth limit: kBuildMaxDepth + 1 levels.
+// rt_build.h holds every line a lane runs, the order of the launches (build_order) and the sizes of the
+// arrays (build_carve); the kernels here supply the lane context (lane index, __syncthreads, integer
+// atomics), and the host path the executor that turns a step of the order into a launch.
 #include "rt_build.h"
 #include "rt_refit.h"
 
@@ -106,87 +91,67 @@ struct Arena {
         return p;
     }
 };
-void carve(Arena &a, uint32_t n, BuildArgs &B) {
-    B.idx2 = a.take<uint32_t>(n);
-    B.ptab = a.take<uint32_t>(n);
-    B.qtab = a.take<uint32_t>(n);
-    B.rk = a.take<uint32_t>(n);
-    B.node = a.take<BNode>(2 * (size_t)n + 2);
-    B.bflag = a.take<uint32_t>((size_t)n + 1);
-    B.csum = a.take<uint32_t>(scan_runs(n) + 1u);
-    B.ctr = a.take<uint32_t>(kCtrWords);
-    B.wacc = a.take<uint32_t>((size_t)build_wide_cap(n) * kAccWords);
-    for (int k = 0; k < 2; ++k) {
-        B.wnode[k] = a.take<WNode>(build_wide_cap(n));
-        B.task[k] = a.take<BTask>(build_task_cap(n));
+// build_order's executor on the device: a step is a launch on the stream; a launch's error shows at the next read
+struct DevExec {
+    const BuildArgs &B;
+    hipStream_t st;
+    int rc = RT_OK;   // of the call that failed, once a method has returned false
+
+    template <class F>
+    bool ok(F call) { return (rc = call()) == RT_OK; }
+    bool zero(uint32_t *p, size_t words) {
+        return ok([&]() -> int {
+            HIP_TRY(hipMemsetAsync(p, 0, sizeof(uint32_t) * words, st));
+            return RT_OK;
+        });
     }
-    B.chunkL = a.take<uint32_t>(build_task_cap(n));
-    B.slist = a.take<uint32_t>((size_t)n + 1);
-    B.depth_of = a.take<uint32_t>(2 * (size_t)n + 2);
-}
+    bool read(uint32_t *dst, const uint32_t *src, size_t words) {
+        return ok([&]() -> int {
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(dst, src, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            return RT_OK;
+        });
+    }
+    bool step(BuildStep s, uint32_t count, uint32_t arg) {
+        const dim3 block(256), lanes((count + 255u) / 256u), wgs(count);
+        switch (s) {
+        case kStepInit: hipLaunchKernelGGL(k_init, lanes, block, 0, st, B); break;
+        case kStepWideBounds: hipLaunchKernelGGL(k_wide_bounds, wgs, block, 0, st, B, arg); break;
+        case kStepWideBins: hipLaunchKernelGGL(k_wide_bins, wgs, block, 0, st, B, arg); break;
+        case kStepWidePlane: hipLaunchKernelGGL(k_wide_plane, wgs, block, 0, st, B, arg); break;
+        case kStepWideSettle: hipLaunchKernelGGL(k_wide_settle, lanes, block, 0, st, B, arg, count); break;
+        case kStepWideTables: hipLaunchKernelGGL(k_wide_tables, wgs, block, 0, st, B, arg); break;
+        case kStepWideMove: hipLaunchKernelGGL(k_wide_move, wgs, block, 0, st, B, arg); break;
+        case kStepWideBack: hipLaunchKernelGGL(k_wide_back, wgs, block, 0, st, B, arg); break;
+        case kStepSubtrees: hipLaunchKernelGGL(k_subtrees, wgs, block, 0, st, B); break;
+        case kStepScanSum: hipLaunchKernelGGL(k_scan_sum, lanes, block, 0, st, B); break;
+        case kStepScanTop: hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(64), 0, st, B); break;
+        case kStepScanApply: hipLaunchKernelGGL(k_scan_apply, lanes, block, 0, st, B); break;
+        case kStepEmit: hipLaunchKernelGGL(k_emit, lanes, block, 0, st, B); break;
+        case kStepPermute: hipLaunchKernelGGL(k_permute, lanes, block, 0, st, B); break;
+        case kStepBoxes: hipLaunchKernelGGL(k_boxes, lanes, block, 0, st, B, count, arg); break;
+        }
+        return true;
+    }
+};
 
 int run_build(const BuildArgs &B, hipStream_t st, const std::string &who, Rebuilt &out) {
-    const uint32_t n = B.n;
-    const dim3 block(256);
-    const dim3 per_prim((n + 255u) / 256u);
-    uint32_t launches = 0;
-    HIP_TRY(hipMemsetAsync(B.ctr, 0, sizeof(uint32_t) * kCtrWords, st));
-    HIP_TRY(hipMemsetAsync(B.bflag, 0, sizeof(uint32_t) * ((size_t)n + 1), st));
-    hipLaunchKernelGGL(k_init, per_prim, block, 0, st, B);
-    ++launches;
-    uint32_t lvl[2] = {0, 0}, levels = 0;   // nodes and tasks of the level
-    HIP_TRY(hipMemcpyAsync(lvl, B.ctr + kCtrLevel, sizeof(lvl), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (uint32_t lv = 0; lvl[0] > 0; ++lv) {
-        if (lv > kBuildMaxDepth) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64");
-        if (lvl[0] > build_wide_cap(n) || lvl[1] > build_task_cap(n)) return fail(RT_ERR_HIP, who + ": level tables overrun");
-        const dim3 tasks(lvl[1]);
-        HIP_TRY(hipMemsetAsync(B.wacc, 0, sizeof(uint32_t) * kAccWords * (size_t)lvl[0], st));
-        hipLaunchKernelGGL(k_wide_bounds, tasks, block, 0, st, B, lv);
-        hipLaunchKernelGGL(k_wide_bins, tasks, block, 0, st, B, lv);
-        hipLaunchKernelGGL(k_wide_plane, tasks, block, 0, st, B, lv);
-        hipLaunchKernelGGL(k_wide_settle, dim3((lvl[0] + 255u) / 256u), block, 0, st, B, lv, lvl[0]);
-        hipLaunchKernelGGL(k_wide_tables, tasks, block, 0, st, B, lv);
-        hipLaunchKernelGGL(k_wide_move, tasks, block, 0, st, B, lv);
-        hipLaunchKernelGGL(k_wide_back, tasks, block, 0, st, B, lv);
-        launches += 7;
-        ++levels;
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(lvl, B.ctr + kCtrLevel + 2u * (lv + 1u), sizeof(lvl), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    uint32_t ctr[kCtrLevel];
-    HIP_TRY(hipMemcpyAsync(ctr, B.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t nsmall = ctr[kCtrSmall];
-    if (nsmall > n) return fail(RT_ERR_HIP, who + ": subtree list overrun");
-    if (nsmall) {
-        hipLaunchKernelGGL(k_subtrees, dim3(nsmall), block, 0, st, B);
-        ++launches;
-    }
-    const dim3 runs((scan_runs(n) + 255u) / 256u);
-    hipLaunchKernelGGL(k_scan_sum, runs, block, 0, st, B);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(64), 0, st, B);
-    hipLaunchKernelGGL(k_scan_apply, runs, block, 0, st, B);
-    hipLaunchKernelGGL(k_emit, per_prim, block, 0, st, B);
-    launches += 4;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ctr, B.ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // take_tree's limits, before anything reads the new node words
-    out.nodes_used = 2u + 2u * ctr[kCtrSplits];
-    out.depth = ctr[kCtrDepth];
-    out.max_leaf = ctr[kCtrMaxLeaf];
-    if ((ctr[kCtrErr] & kBuildErrDepth) || out.depth > kBuildMaxDepth)
-        return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64 (the reference's stack[64])");
-    if (out.max_leaf > 255) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has a leaf with more than 255 primitives");
-    if (out.nodes_used > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has more than 2^24 nodes");
-    hipLaunchKernelGGL(k_permute, per_prim, block, 0, st, B);
-    ++launches;
-    const dim3 per_node((out.nodes_used + 255u) / 256u);
-    for (uint32_t d = out.depth + 1u; d-- > 0u;) {
-        hipLaunchKernelGGL(k_boxes, per_node, block, 0, st, B, out.nodes_used, d);
-        ++launches;
+    DevExec x{B, st};
+    BuildFigures f;
+    const int code = build_order(x, B, f);
+    out.nodes_used = f.nodes_used;
+    out.depth = f.depth;
+    out.max_leaf = f.max_leaf;
+    switch (code) {
+    case kBuildOk: break;
+    case kBuildExec: return x.rc;
+    case kBuildLevels: return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64");
+    case kBuildTableOverrun: return fail(RT_ERR_HIP, who + ": level tables overrun");
+    case kBuildListOverrun: return fail(RT_ERR_HIP, who + ": subtree list overrun");
+    case kBuildDeep: return fail(RT_ERR_UNSUPPORTED, who + ": the new tree is deeper than 64 (the reference's stack[64])");
+    case kBuildWideLeaf: return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has a leaf with more than 255 primitives");
+    case kBuildNodes: return fail(RT_ERR_UNSUPPORTED, who + ": the new tree has more than 2^24 nodes");
     }
     HIP_TRY(hipGetLastError());
     float4 root[2];
@@ -194,11 +159,11 @@ int run_build(const BuildArgs &B, hipStream_t st, const std::string &who, Rebuil
     HIP_TRY(hipStreamSynchronize(st));
     out.root_word = fbits(root[1].z);
     out.finite = true;
-    for (float f : {root[0].x, root[0].y, root[0].z, root[0].w, root[1].x, root[1].y}) out.finite = out.finite && std::isfinite(f);
-    out.stats[0] = levels;
-    out.stats[1] = ctr[kCtrWideSplit];
-    out.stats[2] = nsmall;
-    out.stats[3] = launches;
+    for (float v : {root[0].x, root[0].y, root[0].z, root[0].w, root[1].x, root[1].y}) out.finite = out.finite && std::isfinite(v);
+    out.stats[0] = f.levels;
+    out.stats[1] = f.wide_splits;
+    out.stats[2] = f.subtrees;
+    out.stats[3] = f.launches;
     return RT_OK;
 }
 
@@ -222,19 +187,19 @@ int build_tree(const BuildInputs &in, hipStream_t st, Rebuilt &out) {
     B.old_prims = (const float4 *)in.prims;
     B.margin = in.margin;
     Arena sizes;
-    carve(sizes, n, B);
+    build_carve(sizes, n, B);
     void *work = nullptr;
     auto alloc = [&who](void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? RT_OK : fail(RT_ERR_HIP, who + ": hipMalloc failed"); };
     int rc = alloc(&work, sizes.used);
-    if (rc == RT_OK) rc = alloc(&out.nodes, sizeof(float4) * 2 * (2 * (size_t)n + 2));
-    if (rc == RT_OK) rc = alloc(&out.prims, sizeof(float4) * 3 * (size_t)n);
-    if (rc == RT_OK) rc = alloc(&out.slot_box, sizeof(float4) * 2 * (size_t)n);
-    if (rc == RT_OK) rc = alloc(&out.slot_of, sizeof(uint32_t) * (size_t)n);
-    if (rc == RT_OK) rc = alloc(&out.index, sizeof(uint32_t) * (size_t)n);
+    if (rc == RT_OK) rc = alloc(&out.nodes, sizeof(float4) * build_nodes_len(n));
+    if (rc == RT_OK) rc = alloc(&out.prims, sizeof(float4) * build_prims_len(n));
+    if (rc == RT_OK) rc = alloc(&out.slot_box, sizeof(float4) * build_slot_box_len(n));
+    if (rc == RT_OK) rc = alloc(&out.slot_of, sizeof(uint32_t) * build_ids_len(n));
+    if (rc == RT_OK) rc = alloc(&out.index, sizeof(uint32_t) * build_ids_len(n));
     if (rc == RT_OK) {
         Arena a;
         a.base = (char *)work;
-        carve(a, n, B);
+        build_carve(a, n, B);
         B.idx = (uint32_t *)out.index;
         B.nodes = (float4 *)out.nodes;
         B.prims = (float4 *)out.prims;

@@ -1656,6 +1656,29 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
 }
 
 // ---- the rebuild (rt_build.hip): built into fresh buffers, checked, and only then swapped in
+
+// a Rebuilt's tree becomes the scene's (the splice sets s->num_prims first): the old buffers are freed
+static void swap_in_tree(rt_scene *s, const Rebuilt &t) {
+    RefitState &R = s->refit;
+    for (void *old : {s->d_nodes, s->d_prims, R.d_slot_box, R.d_slot_of, R.d_index})
+        if (old) (void)hipFree(old);
+    s->d_nodes = t.nodes;
+    s->d_prims = t.prims;
+    R.d_slot_box = t.slot_box;
+    R.d_slot_of = t.slot_of;
+    R.d_index = t.index;
+    s->bvh.nodes_used = t.nodes_used;
+    s->bvh.depth = t.depth;
+    s->bvh.max_leaf = t.max_leaf;
+    // the host tree and the refit schedule are the old topology's: the tree is downloaded whole
+    // before its next use, the next update builds its schedule from it
+    R.topo_stale = true;
+    R.refit_ready = false;
+    for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
+    // every box is the union of the finite boxes below it
+    scene_tree_fields(s, t.root_word, true, t.finite);
+}
+
 int rt_scene_rebuild(rt_scene *s, void *stream) {
     const char *who = "rt_scene_rebuild";
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_rebuild: null scene");
@@ -1667,24 +1690,7 @@ int rt_scene_rebuild(rt_scene *s, void *stream) {
     try {
         Rebuilt t;
         if ((rc = rebuild(s->refit, records_of(s), (hipStream_t)stream, t)) != RT_OK) return rc;
-        RefitState &R = s->refit;
-        for (void *old : {s->d_nodes, s->d_prims, R.d_slot_box, R.d_slot_of, R.d_index})
-            if (old) (void)hipFree(old);
-        s->d_nodes = t.nodes;
-        s->d_prims = t.prims;
-        R.d_slot_box = t.slot_box;
-        R.d_slot_of = t.slot_of;
-        R.d_index = t.index;
-        s->bvh.nodes_used = t.nodes_used;
-        s->bvh.depth = t.depth;
-        s->bvh.max_leaf = t.max_leaf;
-        // the host tree and the refit schedule are the old topology's: the tree is downloaded whole
-        // before its next use, the next update builds its schedule from it
-        R.topo_stale = true;
-        R.refit_ready = false;
-        for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
-        // every box is the union of the finite boxes below it
-        scene_tree_fields(s, t.root_word, true, t.finite);
+        swap_in_tree(s, t);
         return RT_OK;
     } catch (const std::exception &e) {
         return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
@@ -1738,28 +1744,16 @@ int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, cons
         std::vector<uint32_t> indices(n, 0u);
         const SpliceEdit e{first, remove, insert, prims_dev, s->num_materials};
         if ((rc = splice(R, records_of(s), e, (hipStream_t)stream, t)) != RT_OK) return rc;
-        for (void *old : {s->d_nodes, s->d_prims, s->d_shade, R.d_slot_box, R.d_slot_of, R.d_index, R.d_cen})
+        // the splice's own: the new id space and the host's share of it; then the tree, as after a rebuild
+        for (void *old : {s->d_shade, R.d_cen})
             if (old) (void)hipFree(old);
-        s->d_nodes = t.nodes;
-        s->d_prims = t.prims;
         s->d_shade = t.shade;
-        R.d_slot_box = t.slot_box;
-        R.d_slot_of = t.slot_of;
-        R.d_index = t.index;
         R.d_cen = t.cen;
+        s->view.shade = (const float4 *)s->d_shade;
         s->num_prims = n;
         R.pinfo.swap(pinfo);
         s->bvh.indices.swap(indices);
-        s->bvh.nodes_used = t.nodes_used;
-        s->bvh.depth = t.depth;
-        s->bvh.max_leaf = t.max_leaf;
-        // as after a rebuild: the host tree is downloaded whole before its next use, the next update
-        // builds its schedule from it
-        R.topo_stale = true;
-        R.refit_ready = false;
-        for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
-        s->view.shade = (const float4 *)s->d_shade;
-        scene_tree_fields(s, t.root_word, true, t.finite);
+        swap_in_tree(s, t);
         return RT_OK;
     } catch (const std::exception &e) {
         free_rebuilt(t);

@@ -13,42 +13,12 @@
 #include <cstdio>
 #include <vector>
 
+#include "scene_util.h"
 #include "update_util.h"
 
 using namespace rt;
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED: %s (line %d): %s\n", #c, __LINE__, rt_last_error()); return 1; } } while (0)
-
-static rt_material material(int kind) {
-    rt_material m{};
-    m.kind = kind;
-    m.color[0] = m.color[1] = m.color[2] = 0.8f;
-    m.diffuse = -1.0f;
-    return m;
-}
-static const std::vector<rt_material> kMats = {material(RT_LIGHT), material(RT_DIFFUSE), material(RT_MIRROR)};
-static rt_prim sphere(float x, float y, float z, float r, int mat) { return rt_prim{RT_SPHERE, mat, {x, y, z, r}}; }
-static rt_prim tri(std::initializer_list<float> v, int mat) {
-    rt_prim p{RT_TRIANGLE, mat, {}};
-    int k = 0;
-    for (float f : v) p.v[k++] = f;
-    return p;
-}
-// tests/scenes_util.py kat_scene
-static std::vector<rt_prim> kat_prims() {
-    return {sphere(0, 4, -2, 0.5f, 0), tri({0, 0, 5, 1, 0, 5, 0, 1, 5}, 1), tri({1, 0, 5, 1, 1, 5, 0, 1, 5}, 1),
-            tri({-2, -1, 7, -1, -1, 7, -2, 0, 7}, 1), tri({-2, -1, 7, -1, -1, 7, -2, 0, 7}, 2), sphere(3, 0, 5, 1.0f, 2),
-            sphere(-3, 2, 5, 0.25f, 1), rt_prim{RT_PLANE, 1, {0, 1, 0, 2.0f}}};
-}
-
-static int pack(const std::vector<rt_prim> &p, const std::vector<rt_material> &m, const float *T, const Bvh *tree, ScenePack &out) {
-    rt_scene_desc d{};
-    d.prims = p.data(); d.num_prims = (uint32_t)p.size();
-    d.materials = m.data(); d.num_materials = (uint32_t)m.size();
-    d.transforms = T;
-    if (tree) { d.bvh_nodes = tree->nodes.data(); d.bvh_num_nodes = tree->nodes_used; d.bvh_indices = tree->indices.data(); }
-    return pack_scene(&d, PackOptions(), out);
-}
 
 // ------------------------------------------------------------------------------------- the plan
 
@@ -185,16 +155,6 @@ static bool run_update(HostScene &h, const Src &src, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) src.write(h.A, i);
     h.refit();
     return true;
-}
-
-// twist about y by k radians per unit of y (tools/refit_time.py)
-static void twist(const float in[9], float k, float out[9]) {
-    for (int v = 0; v < 3; ++v) {
-        const double x = in[3 * v], y = in[3 * v + 1], z = in[3 * v + 2], a = (double)k * y, c = std::cos(a), s = std::sin(a);
-        out[3 * v] = (float)(c * x - s * z);
-        out[3 * v + 1] = (float)y;
-        out[3 * v + 2] = (float)(s * x + c * z);
-    }
 }
 
 static int tri_verts(const SceneSource &teapot, const ScenePack &at0, uint32_t first, uint32_t ntri) {

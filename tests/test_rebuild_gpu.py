@@ -113,7 +113,9 @@ def test_fresh_scene_rebuilds_to_the_hosts_tree(rt, torch, cases, name):
     assert g.info == twin.info
     st = g.rebuild_stats()
     print(name, "rebuild stats", st)
-    if name == "soup":                                   # both kernel paths ran
+    # the launch order: init, seven steps a level, the subtrees if any, three scans and emit, permute, a box pass per depth
+    assert st[3] == 1 + 7 * st[0] + (1 if st[2] else 0) + 4 + 1 + (g.info["depth"] + 1)
+    if name == "soup":                                  # both kernel paths ran
         assert st[0] >= 2 and st[1] > 0 and st[2] > 0
     if name == "leaf":                                   # the one-leaf tree was split, by one workgroup
         assert g.info["nodes_used"] > 2 and st[1] == 0 and st[2] == 1
