@@ -151,6 +151,11 @@ def lib():
         "rt_scene_transform_triangles": ([vp, C.POINTER(TriXform), u32, vp, vp], C.c_int),
         "rt_scene_rebuild": ([vp, vp], C.c_int),
         "rt_scene_rebuild_stats": ([vp, C.POINTER(C.c_uint32)], C.c_int),
+        "rt_scene_prepare_updates": ([vp, vp], C.c_int),
+        "rt_scene_update_plan_info": ([vp, C.POINTER(C.c_uint32)], C.c_int),
+        "rt_scene_copy_update_plan": ([vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], C.c_int),
+        "rt_bvh_refit_plan_host": ([vp, u32, C.POINTER(u32), u32, C.POINTER(C.POINTER(u32)), C.POINTER(C.POINTER(u32)),
+                                    C.POINTER(C.POINTER(u32)), C.POINTER(u32)], C.c_int),
         "rt_scene_splice_triangles": ([vp, u32, u32, vp, u32, vp], C.c_int),
         "rt_scene_splice_triangles_host": ([vp, u32, u32, C.POINTER(Prim), u32], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
@@ -403,6 +408,31 @@ def bvh_cost_host(nodes):
     return _cost_dict(c)
 
 
+PLAN_ROUTES = ("none", "host", "gpu_launches", "gpu_one_workgroup")   # rt_scene_update_plan_info's second word
+PLAN_SMALL_NODES = 2048   # kPlanSmall (csrc/rt_plan.h): trees up to this many nodes take the one-workgroup route
+
+
+def refit_plan_host(nodes, indices):
+    """rt_bvh_refit_plan_host: the refit schedule of a plain tree (nodes [n, 32] uint8 and indices as
+    build_bvh_host / Scene.bvh return them) as a dict -- list, lvl, grp (uint32 arrays), ntreelets,
+    has_top.  What Scene.update_plan() equals word for word."""
+    L = lib()
+    N = np.ascontiguousarray(nodes, np.uint8).reshape(-1, 32)
+    ix = np.ascontiguousarray(indices, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    ptr = [u32p(), u32p(), u32p()]
+    counts = (C.c_uint32 * 4)()
+    _check(L.rt_bvh_refit_plan_host(N.ctypes.data_as(C.c_void_p), len(N), ix.ctypes.data_as(u32p), len(ix),
+                                    C.byref(ptr[0]), C.byref(ptr[1]), C.byref(ptr[2]), counts))
+    try:
+        lens = (counts[0], counts[1], counts[2] + 2)
+        out = [np.ctypeslib.as_array(q, shape=(n,)).copy() if n else np.zeros(0, np.uint32) for q, n in zip(ptr, lens)]
+    finally:
+        for q in ptr:
+            L.rt_free(C.cast(q, C.c_void_p))
+    return {"list": out[0], "lvl": out[1], "grp": out[2], "ntreelets": int(counts[2]), "has_top": bool(counts[3])}
+
+
 def _info_dict(info):
     return {"num_prims": info.num_prims, "nodes_used": info.nodes_used, "depth": info.depth, "max_leaf": info.max_leaf,
             "num_refs": info.num_refs}
@@ -647,6 +677,31 @@ class Scene:
         out = (C.c_uint32 * 4)()
         _check(self.L.rt_scene_rebuild_stats(self.h, out))
         return [int(x) for x in out]
+
+    def prepare_updates(self, stream=None):
+        """rt_scene_prepare_updates: the update state and the refit schedule of the current topology on
+        the device now, built on the GPU, so that the next update_* / transform_triangles call costs what
+        a later one costs.  Blocks; idempotent.  Returns the kernel launches it made (0: all stood ready).
+        stream: a hipStream_t handle (None: the null stream)."""
+        _check(self.L.rt_scene_prepare_updates(self.h, C.c_void_p(stream)))
+        return self.update_plan_info()["launches"]
+
+    def update_plan_info(self):
+        """rt_scene_update_plan_info as a dict: ready, route (one of PLAN_ROUTES), ntreelets, has_top,
+        list_len, lvl_len, top_nodes, launches."""
+        out = (C.c_uint32 * 8)()
+        _check(self.L.rt_scene_update_plan_info(self.h, out))
+        return {"ready": bool(out[0]), "route": PLAN_ROUTES[out[1]], "ntreelets": int(out[2]), "has_top": bool(out[3]),
+                "list_len": int(out[4]), "lvl_len": int(out[5]), "top_nodes": int(out[6]), "launches": int(out[7])}
+
+    def update_plan(self):
+        """rt_scene_copy_update_plan: the schedule on the device, as refit_plan_host returns it."""
+        i = self.update_plan_info()
+        if not i["ready"]:
+            raise RTError(RT_ERR_INVALID, "update_plan: no schedule is ready (prepare_updates)")
+        out = [np.zeros(n, np.uint32) for n in (i["list_len"], i["lvl_len"], i["ntreelets"] + 2)]
+        _check(self.L.rt_scene_copy_update_plan(self.h, *[a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in out]))
+        return {"list": out[0], "lvl": out[1], "grp": out[2], "ntreelets": i["ntreelets"], "has_top": i["has_top"]}
 
     def splice_triangles(self, first, remove, prims, stream=None):
         """rt_scene_splice_triangles: triangle primitives [first, first + remove) leave, the triangles of

@@ -1780,6 +1780,48 @@ int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {
     return RT_OK;
 }
 
+// ---- the refit schedule ahead of the first update (rt_plan.hip)
+
+int rt_scene_prepare_updates(rt_scene *s, void *stream) {
+    const char *who = "rt_scene_prepare_updates";
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_prepare_updates: null scene");
+    const int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return prepare_updates(s->refit, records_of(s), (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_update_plan_info(const rt_scene *s, uint32_t out[8]) {
+    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_update_plan_info: null argument");
+    const RefitState &R = s->refit;
+    const PlanInfo none{}, &p = R.refit_ready ? R.plan_info : none;
+    out[0] = R.refit_ready ? 1u : 0u;
+    out[1] = p.route;
+    out[2] = R.refit_ready ? R.plan.ntreelets : 0u;
+    out[3] = R.refit_ready && R.plan.has_top ? 1u : 0u;
+    out[4] = p.list_len;
+    out[5] = p.lvl_len;
+    out[6] = p.top_nodes;
+    out[7] = p.launches;
+    return RT_OK;
+}
+
+int rt_scene_copy_update_plan(const rt_scene *s, uint32_t *list, uint32_t *lvl, uint32_t *grp) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: null scene");
+    const RefitState &R = s->refit;
+    if (!R.refit_ready) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: no schedule is ready (rt_scene_prepare_updates)");
+    HIP_TRY(hipSetDevice(s->device));
+    // the schedule's builder and every update block, so the arrays are settled
+    if (list) HIP_TRY(hipMemcpy(list, R.d_list, sizeof(uint32_t) * R.plan_info.list_len, hipMemcpyDeviceToHost));
+    if (lvl) HIP_TRY(hipMemcpy(lvl, R.d_lvl, sizeof(uint32_t) * R.plan_info.lvl_len, hipMemcpyDeviceToHost));
+    if (grp) HIP_TRY(hipMemcpy(grp, R.d_grp, sizeof(uint32_t) * ((size_t)R.plan.ntreelets + 2), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {
     if (!s || (n && (!rays || !hits))) return fail(RT_ERR_INVALID, "rt_intersect: null argument");
     if (n == 0) return RT_OK;

@@ -43,6 +43,10 @@ struct RefitPlan {
 };
 // false when the tree is not a plain one (a primitive in no leaf or in two)
 bool build_refit_plan(const Bvh &b, uint32_t num_prims, RefitPlan &out);
+// where and how the schedule on the device was built (rt_scene_update_plan_info): route 0 none,
+// 1 host (build_refit_plan, uploaded), 2 GPU in many launches, 3 GPU in one workgroup (rt_plan.h);
+// launches: of the call that last asked for the schedule -- 0 where it stood ready
+struct PlanInfo { uint32_t route = 0, list_len = 0, lvl_len = 0, top_nodes = 0, launches = 0; };
 // the slot boxes a refit starts from: per leaf slot k the box and sticky flag (pbox, pinfo of
 // ScenePack) of primitive indices[k]
 void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std::vector<float> &pbox, std::vector<float4> &out);
@@ -51,7 +55,8 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 // type | sticky << 7 (mark_sticky) and its box (prim_geometry; 6 floats) -- what a refit needs of
 // the primitives that do not move -- and its centroid, which a rebuild bins by.  The first update or
 // rebuild puts slot map, slot boxes and centroids on the device, where they live from there on; the
-// schedule is built by the first update and again by the first after a rebuild (rt_build.hip).
+// schedule is built on the device (rt_plan.hip) by rt_scene_prepare_updates or else by the first
+// update, and again after a rebuild (rt_build.hip).
 struct RefitState {
     std::vector<uint8_t> pinfo;
     std::vector<float> pbox;
@@ -60,7 +65,8 @@ struct RefitState {
     bool boxes_finite = true;       // every primitive box was finite at creation
     bool state_ready = false;       // slot_of, slot_box and cen are on the device (and authoritative from there on)
     bool refit_ready = false;       // ... and so is the schedule of the current topology
-    RefitPlan plan;
+    RefitPlan plan;                 // ntreelets and has_top of the device schedule (the vectors are not kept)
+    PlanInfo plan_info;
     void *d_cen = nullptr;          // per id its centroid (float4)
     void *d_index = nullptr;        // after a rebuild: the new primitive-index array (slot -> id)
     bool topo_stale = false;        // a rebuild changed the topology: the host tree is downloaded whole before its next use
@@ -118,6 +124,15 @@ int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hip
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
                  hipStream_t st, const char *refusal, bool *finite);
 
+
+// The schedule of the current topology (d_list, d_lvl, d_grp, plan.ntreelets, plan.has_top) built
+// on `st` from the device node array (rt_plan.hip); blocks.  The host tree is neither read nor
+// downloaded.  RT_OK with refit_ready still false: the nodes reached from the root are no tree
+// (rt_plan.h, kPlanNotTree) and the caller takes the host's walk.
+int plan_on_device(RefitState &R, const SceneRecords &S, hipStream_t st);
+// rt_scene_prepare_updates: the update state and the schedule on the device now; blocks like an
+// update, launches nothing where both stand ready
+int prepare_updates(RefitState &R, const SceneRecords &S, hipStream_t st);
 
 // the host tree from the device's after a refit (boxes) or a rebuild (nodes and indices)
 int sync_host_tree(RefitState &R, Bvh &b, const void *d_nodes);

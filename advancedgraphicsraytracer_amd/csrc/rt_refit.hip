@@ -47,18 +47,18 @@ __device__ __forceinline__ void refit_group(const RefitArgs &A, uint32_t g) {
 __global__ void __launch_bounds__(256) k_refit_treelets(RefitArgs A) { refit_group(A, blockIdx.x); }
 __global__ void __launch_bounds__(1024) k_refit_top(RefitArgs A, uint32_t g) { refit_group(A, g); }
 
-// the refit schedule of the current topology and its device arrays: on the first update of a scene
-// and on the first after a rebuild (the slot map, the slot boxes and the centroids stay the device's)
-int ensure_refit(RefitState &R, const SceneRecords &S) {
+// the refit schedule of the current topology on the device: built there (rt_plan.hip) on the first
+// update of a scene and on the first after a rebuild, unless rt_scene_prepare_updates did so before
+// (the slot map, the slot boxes and the centroids stay the device's)
+int ensure_refit(RefitState &R, const SceneRecords &S, hipStream_t st) {
     if (R.refit_ready) return RT_OK;
-    int rc = sync_host_tree(R, *S.bvh, S.nodes);
+    int rc = ensure_state(R, S);
     if (rc != RT_OK) return rc;
+    if ((rc = plan_on_device(R, S, st)) != RT_OK || R.refit_ready) return rc;
+    // no tree (a child pair with two parents in a caller's prebuilt node array): the host's walk
+    // schedules what it meets, as it always did
+    if ((rc = sync_host_tree(R, *S.bvh, S.nodes)) != RT_OK) return rc;
     if (!build_refit_plan(*S.bvh, S.num_prims, R.plan)) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
-    if ((rc = ensure_state(R, S)) != RT_OK) return rc;
-    for (void **p : {&R.d_list, &R.d_lvl, &R.d_grp}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
     rc = upload(&R.d_list, R.plan.list);
     if (rc == RT_OK) rc = upload(&R.d_lvl, R.plan.lvl);
     if (rc == RT_OK) rc = upload(&R.d_grp, R.plan.grp);
@@ -69,6 +69,8 @@ int ensure_refit(RefitState &R, const SceneRecords &S) {
         }
         return rc;
     }
+    const uint32_t listed = (uint32_t)R.plan.list.size();
+    R.plan_info = PlanInfo{1u, listed, (uint32_t)R.plan.lvl.size(), listed - R.plan.lvl[R.plan.grp[R.plan.ntreelets]], 0u};
     for (std::vector<uint32_t> *v : {&R.plan.slot_of, &R.plan.list, &R.plan.lvl, &R.plan.grp}) std::vector<uint32_t>().swap(*v);
     R.refit_ready = true;
     return RT_OK;
@@ -91,11 +93,13 @@ RefitArgs refit_args(const RefitState &R, const SceneRecords &S) {
 int ensure_state(RefitState &R, const SceneRecords &S) {
     if (R.state_ready) return RT_OK;
     // never updated, never rebuilt: the host tree and creation's per-primitive copies are current
-    std::vector<uint32_t> slot_of(S.num_prims, 0u);
+    // a plain tree holds every id in exactly one slot (a tree out of build_tree does by construction)
+    std::vector<uint32_t> slot_of(S.num_prims, ~0u);
     if (S.bvh->indices.size() != S.num_prims) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
     for (uint32_t k = 0; k < S.num_prims; ++k) {
-        if (S.bvh->indices[k] >= S.num_prims) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
-        slot_of[S.bvh->indices[k]] = k;
+        const uint32_t id = S.bvh->indices[k];
+        if (id >= S.num_prims || slot_of[id] != ~0u) return fail(RT_ERR_UNSUPPORTED, "refit: not a plain tree");
+        slot_of[id] = k;
     }
     std::vector<float4> box, cen(S.num_prims);
     seed_slot_boxes(*S.bvh, R.pinfo, R.pbox, box);
@@ -141,6 +145,15 @@ int sync_host_tree(RefitState &R, Bvh &b, const void *d_nodes) {
     return RT_OK;
 }
 
+int prepare_updates(RefitState &R, const SceneRecords &S, hipStream_t st) {
+    HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
+    if (R.refit_ready) {
+        R.plan_info.launches = 0u;
+        return RT_OK;
+    }
+    return ensure_refit(R, S, st);
+}
+
 void free_refit(RefitState &R) {
     R.state_ready = false;
     for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp, &R.d_flag, &R.d_ranges, &R.d_cen, &R.d_index}) {
@@ -149,13 +162,14 @@ void free_refit(RefitState &R) {
     }
     R.ranges_bytes = 0;
     R.refit_ready = false;
+    R.plan_info = PlanInfo{};
 }
 
 template <class Src>
 int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *refusal,
            const UpdateCopy *copies, int ncopies, bool *finite) {
     HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
-    int rc = ensure_refit(R, S);
+    int rc = ensure_refit(R, S, st);
     if (rc != RT_OK) return rc;
     const RefitArgs A = refit_args(R, S);
     const dim3 grid((n + 255u) / 256u), block(256);

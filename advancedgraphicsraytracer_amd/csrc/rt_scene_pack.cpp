@@ -4,6 +4,7 @@
 // result.  The record layouts are in rt_device.hip's header comment, their encoders in rt_records.h.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -460,3 +461,38 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 }
 
 }  // namespace rt
+
+// build_refit_plan through the C-ABI: the definition the device schedule (rt_plan.h) is compared with
+extern "C" int rt_bvh_refit_plan_host(const void *nodes, uint32_t nodes_used, const uint32_t *indices, uint32_t n,
+                                      uint32_t **list, uint32_t **lvl, uint32_t **grp, uint32_t counts[4]) {
+    using namespace rt;
+    if (!nodes || !indices || !list || !lvl || !grp || !counts || n == 0 || nodes_used < 2)
+        return fail(RT_ERR_INVALID, "rt_bvh_refit_plan_host: null or empty argument");
+    *list = *lvl = *grp = nullptr;
+    try {
+        Bvh b;
+        b.nodes.resize(nodes_used);
+        std::memcpy(b.nodes.data(), nodes, sizeof(Node) * nodes_used);
+        b.indices.assign(indices, indices + n);
+        b.nodes_used = nodes_used;
+        RefitPlan p;
+        if (!build_refit_plan(b, n, p)) return fail(RT_ERR_UNSUPPORTED, "rt_bvh_refit_plan_host: not a plain tree");
+        uint32_t **dst[3] = {list, lvl, grp};
+        const std::vector<uint32_t> *src[3] = {&p.list, &p.lvl, &p.grp};
+        for (int k = 0; k < 3; ++k) {
+            *dst[k] = static_cast<uint32_t *>(std::malloc(sizeof(uint32_t) * std::max<size_t>(1, src[k]->size())));
+            if (!*dst[k]) {
+                for (int j = 0; j < k; ++j) { std::free(*dst[j]); *dst[j] = nullptr; }
+                return fail(RT_ERR_INVALID, "rt_bvh_refit_plan_host: out of memory");
+            }
+            std::memcpy(*dst[k], src[k]->data(), sizeof(uint32_t) * src[k]->size());
+        }
+        counts[0] = (uint32_t)p.list.size();
+        counts[1] = (uint32_t)p.lvl.size();
+        counts[2] = p.ntreelets;
+        counts[3] = p.has_top ? 1u : 0u;
+        return RT_OK;
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_bvh_refit_plan_host: ") + e.what());
+    }
+}

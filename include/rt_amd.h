@@ -186,6 +186,16 @@ typedef struct {
 } rt_bvh_cost;
 /* no device: the cost of a BVHNode array (rt_bvh_build_host's, rt_scene_copy_bvh's) */
 int rt_bvh_cost_host(const void *nodes, uint32_t nodes_used, rt_bvh_cost *out);
+/* no device: the refit schedule of a plain tree (nodes_used x 32 B BVHNode, n primitive indices), the
+ * definition rt_scene_copy_update_plan's arrays equal word for word.  list: node indices, treelet after
+ * treelet (whole subtrees of at most 256 nodes, in pre-order of their roots), each sorted by height
+ * above its deepest leaf, then the nodes above the cut, sorted the same way; lvl: per group the start
+ * of each height in list and the group's end; grp: per group its first entry in lvl, the nodes above
+ * the cut being group ntreelets, and one closing entry.  Library-allocated, free each with rt_free.
+ * counts = list length, lvl length, ntreelets, has_top.  RT_ERR_UNSUPPORTED: a primitive in no leaf
+ * slot or in two, or a node array that does not walk. */
+int rt_bvh_refit_plan_host(const void *nodes, uint32_t nodes_used, const uint32_t *indices, uint32_t n,
+                           uint32_t **list, uint32_t **lvl, uint32_t **grp, uint32_t counts[4]);
 /* the opt-in spatial-split BVH (RT_BVH_SBVH) on the host: library-allocated nodes
  * (info->nodes_used x 32 B) and primitive-index array (info->num_refs; primitives may
  * repeat); free both with rt_free */
@@ -234,7 +244,8 @@ int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
  * the scene is ready for any stream.  The caller renders the next frame with reset = 1, as the
  * reference does (renderer.cpp:237).  Renderers keep their timed choices, tile orders and deals
  * (speed only; frames are identical under any of them), and the scene keeps its camera-walk policy.
- * The first update of a scene builds its refit plan (host, one pass over the tree).
+ * The first update of a scene builds its refit schedule on the GPU, unless rt_scene_prepare_updates
+ * did so at a moment of the caller's choosing.
  *   RT_ERR_INVALID      null pointer, range outside the primitives, a non-triangle primitive in the
  *                       range, or a NaN / infinite vertex -- the scene is untouched (the vertices are
  *                       checked in a pass of their own before anything is written);
@@ -291,11 +302,31 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
  *                       depth > 64, > 2^24 nodes) -- the scene is untouched;
  *   RT_ERR_INVALID      null scene.
  * Renderers keep their timed choices and tile orders; the scene keeps its camera-walk policy where
- * the new tree still admits it.  The next in-place update rebuilds its refit schedule. */
+ * the new tree still admits it.  The next in-place update rebuilds its refit schedule (or
+ * rt_scene_prepare_updates, before it). */
 int rt_scene_rebuild(rt_scene *s, void *stream);
 /* diagnostics of the last rebuild: out[0] tree levels processed, out[1] nodes split by the
  * many-workgroup path, out[2] subtrees finished by the one-workgroup path, out[3] kernel launches */
 int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]);
+/* Put what the in-place updates need on the device NOW: the update state (slot map, slot boxes,
+ * centroids) and the refit schedule of the current topology, built on the GPU from the device node
+ * array.  Without this call the first rt_scene_update_* / rt_scene_transform_triangles after
+ * creation, after rt_scene_rebuild and after rt_scene_splice_triangles does the same work inside
+ * itself; with it that update costs what a later one costs.  Blocks like an update (waits for the
+ * scene's device, runs on `stream`).  Idempotent: on an unchanged topology a second call launches
+ * nothing.  Frames are unaffected.
+ *   RT_ERR_UNSUPPORTED  where an update would return it (an SBVH or RT_PT_QUADS=1 scene) -- the
+ *                       scene is untouched;
+ *   RT_ERR_INVALID      null scene. */
+int rt_scene_prepare_updates(rt_scene *s, void *stream);
+/* the schedule on the device: out[0] ready (0 / 1), out[1] where it was built (0 none, 1 host,
+ * 2 GPU in many launches, 3 GPU in one workgroup), out[2] ntreelets, out[3] has_top, out[4] list
+ * length, out[5] lvl length, out[6] nodes above the cut, out[7] kernel launches of the call that last
+ * asked for it (0 where it stood ready).  All 0 while none is ready (a rebuild or a splice drops it). */
+int rt_scene_update_plan_info(const rt_scene *s, uint32_t out[8]);
+/* download the schedule (rt_bvh_refit_plan_host's arrays: out[4] / out[5] / out[2] + 2 words); a
+ * null pointer skips that array.  RT_ERR_INVALID when no schedule is ready. */
+int rt_scene_copy_update_plan(const rt_scene *s, uint32_t *list, uint32_t *lvl, uint32_t *grp);
 /* Add and remove triangles in a live scene.  Remove triangle primitives [first, first + remove) and
  * insert `insert` new triangles at id `first`; primitives behind the edit shift by insert - remove.
  * prims_dev: DEVICE rt_prim[insert] (type RT_TRIANGLE, v[0..8] world-space A, B, C, material an index

@@ -292,6 +292,10 @@ class Scene {   // template/scene.h:37
     // Scene::BuildBVH (template/scene.h:845): the tree of the current primitives, rebuilt on the GPU after
     // in-place updates have moved them; the next Tick resets the accumulator
     void BuildBVH(void *stream = nullptr) { rt_check(rt_scene_rebuild(handle(), stream)); }
+    // everything the in-place updates need on the device now (the refit schedule of the current tree, built
+    // on the GPU): call it after construction, BuildBVH or SpliceTriangles, at a moment of the host's
+    // choosing, and the next Update* / TransformTriangles costs what a later one costs
+    void PrepareUpdates(void *stream = nullptr) { rt_check(rt_scene_prepare_updates(handle(), stream)); }
     // calculateNodeCost (template/scene.h:203-207) summed over the current device tree, on the GPU:
     // compare .sah after in-place updates with its value after the last BuildBVH
     rt_bvh_cost BVHCost(void *stream = nullptr) {
