@@ -55,6 +55,11 @@ class TriXform(C.Structure):
     _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("M", C.c_float * 16)]
 
 
+class TriEdit(C.Structure):
+    """rt_tri_edit: triangles [first, first + remove) leave, `insert` triangles enter at `first`"""
+    _fields_ = [("first", C.c_uint32), ("remove", C.c_uint32), ("insert", C.c_uint32)]
+
+
 class Material(C.Structure):
     _fields_ = [("kind", C.c_int32), ("color", C.c_float * 3), ("color2", C.c_float * 3), ("ior", C.c_float),
                 ("diffuse", C.c_float), ("texture", C.c_int32)]
@@ -158,6 +163,10 @@ def lib():
                                     C.POINTER(C.POINTER(u32)), C.POINTER(u32)], C.c_int),
         "rt_scene_splice_triangles": ([vp, u32, u32, vp, u32, vp], C.c_int),
         "rt_scene_splice_triangles_host": ([vp, u32, u32, C.POINTER(Prim), u32], C.c_int),
+        "rt_scene_splice_ranges": ([vp, C.POINTER(TriEdit), u32, vp, vp], C.c_int),
+        "rt_scene_splice_ranges_host": ([vp, C.POINTER(TriEdit), u32, C.POINTER(Prim)], C.c_int),
+        "rt_scene_compact_triangles": ([vp, vp, vp], C.c_int),
+        "rt_scene_compact_triangles_host": ([vp, vp], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -724,6 +733,68 @@ class Scene:
         prims = list(prims)
         arr = (Prim * len(prims))(*prims) if prims else None
         _check(self.L.rt_scene_splice_triangles_host(self.h, first, remove, arr, len(prims)))
+
+    def splice_ranges(self, edits, stream=None):
+        """rt_scene_splice_ranges: several splice_triangles edits in one rebuild.  edits: a list of
+        (first, remove, prims) in any order, every `first` an id of the scene as it is now; prims a list
+        of triangle() records (staged by the library).  Or a list of (first, remove, recs, insert) with
+        ONE torch tensor [total, 11] of 32-bit words on the scene's device (pack_prims' layout) holding
+        every edit's records back to back in the order of `edits`: pass it as `recs` of any edit (None
+        in the others) and each edit's record count as `insert`.  Ranges must not overlap and no two
+        edits may share a `first`.  Blocks; render the next frame with reset=True."""
+        torch = _torch()
+        edits = [tuple(e) for e in edits]
+        arr = (TriEdit * max(len(edits), 1))()
+        if edits and all(len(e) == 4 for e in edits):
+            recs = [e[2] for e in edits if e[2] is not None]
+            total = sum(int(e[3]) for e in edits)
+            if any(r is not recs[0] for r in recs) or (total and not recs):
+                raise RTError(RT_ERR_INVALID, "splice_ranges: one tensor holds the records of all edits")
+            rec = recs[0] if recs else None
+            if rec is not None:
+                if not isinstance(rec, torch.Tensor) or not rec.is_cuda or rec.device.index != self.device:
+                    raise RTError(RT_ERR_INVALID, "splice_ranges: the records must be a tensor on the scene's device")
+                if rec.element_size() != 4 or rec.dim() != 2 or rec.shape[1] != 11 or rec.shape[0] != total:
+                    raise RTError(RT_ERR_INVALID, "splice_ranges: records must be [sum of the counts, 11] 32-bit words")
+                rec = rec.contiguous()
+            for k, (f, n, _, m) in enumerate(edits):
+                arr[k].first, arr[k].remove, arr[k].insert = int(f), int(n), int(m)
+            s = stream if stream is not None else torch.cuda.current_stream(f"cuda:{self.device}").cuda_stream
+            _check(self.L.rt_scene_splice_ranges(self.h, arr, len(edits), C.c_void_p(rec.data_ptr()) if total else None,
+                                                 C.c_void_p(s)))
+            return
+        prims = []
+        for k, (f, n, new) in enumerate(edits):
+            if isinstance(new, torch.Tensor):
+                raise RTError(RT_ERR_INVALID, "splice_ranges: with a tensor every edit is (first, remove, recs, insert)")
+            new = list(new)
+            arr[k].first, arr[k].remove, arr[k].insert = int(f), int(n), len(new)
+            prims += new
+        recs = (Prim * len(prims))(*prims) if prims else None
+        _check(self.L.rt_scene_splice_ranges_host(self.h, arr, len(edits), recs))
+
+    def compact_triangles(self, keep, stream=None):
+        """rt_scene_compact_triangles: primitive i stays where keep[i] != 0, the survivors keep their
+        order, and the tree is rebuilt once on the GPU.  keep: num_prims flags, a numpy bool / uint8
+        array (staged by the library) or a uint8 / bool torch tensor on the scene's device -- the mask
+        of a GPU pass never travels through the host as ranges.  Only triangles may leave, and never
+        primitive 0; a mask that keeps everything does nothing.  Blocks; render the next frame with
+        reset=True."""
+        torch = _torch()
+        n = self.info["num_prims"]
+        if isinstance(keep, torch.Tensor):
+            if not keep.is_cuda or keep.device.index != self.device:
+                raise RTError(RT_ERR_INVALID, "compact_triangles: the tensor must be on the scene's device")
+            if keep.dtype not in (torch.uint8, torch.bool) or keep.numel() != n:
+                raise RTError(RT_ERR_INVALID, "compact_triangles: keep must be num_prims uint8 flags")
+            k = keep.contiguous()
+            s = stream if stream is not None else torch.cuda.current_stream(k.device).cuda_stream
+            _check(self.L.rt_scene_compact_triangles(self.h, C.c_void_p(k.data_ptr()), C.c_void_p(s)))
+            return
+        k = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+        if k.size != n:
+            raise RTError(RT_ERR_INVALID, "compact_triangles: keep must be num_prims flags")
+        _check(self.L.rt_scene_compact_triangles_host(self.h, k.ctypes.data_as(C.c_void_p)))
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

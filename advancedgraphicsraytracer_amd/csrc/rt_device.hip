@@ -1723,6 +1723,21 @@ static int splice_arguments(const rt_scene *s, uint32_t first, uint32_t remove, 
     return RT_OK;
 }
 
+// a splice's own: the new id space and the host's share of it (pinfo, indices: made by the caller
+// before anything is swapped); then the tree, as after a rebuild
+static void swap_in_splice(rt_scene *s, const Rebuilt &t, std::vector<uint8_t> &pinfo, std::vector<uint32_t> &indices) {
+    RefitState &R = s->refit;
+    for (void *old : {s->d_shade, R.d_cen})
+        if (old) (void)hipFree(old);
+    s->d_shade = t.shade;
+    R.d_cen = t.cen;
+    s->view.shade = (const float4 *)s->d_shade;
+    s->num_prims = (uint32_t)pinfo.size();
+    R.pinfo.swap(pinfo);
+    s->bvh.indices.swap(indices);
+    swap_in_tree(s, t);
+}
+
 int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert,
                               void *stream) {
     const char *who = "rt_scene_splice_triangles";
@@ -1744,16 +1759,7 @@ int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, cons
         std::vector<uint32_t> indices(n, 0u);
         const SpliceEdit e{first, remove, insert, prims_dev, s->num_materials};
         if ((rc = splice(R, records_of(s), e, (hipStream_t)stream, t)) != RT_OK) return rc;
-        // the splice's own: the new id space and the host's share of it; then the tree, as after a rebuild
-        for (void *old : {s->d_shade, R.d_cen})
-            if (old) (void)hipFree(old);
-        s->d_shade = t.shade;
-        R.d_cen = t.cen;
-        s->view.shade = (const float4 *)s->d_shade;
-        s->num_prims = n;
-        R.pinfo.swap(pinfo);
-        s->bvh.indices.swap(indices);
-        swap_in_tree(s, t);
+        swap_in_splice(s, t, pinfo, indices);
         return RT_OK;
     } catch (const std::exception &e) {
         free_rebuilt(t);
@@ -1772,6 +1778,120 @@ int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove,
         HIP_TRY(hipMemcpyAsync(s->d_scratch, prims, sizeof(rt_prim) * (size_t)insert, hipMemcpyHostToDevice, s->stream));
     }
     return rt_scene_splice_triangles(s, first, remove, insert ? (const rt_prim *)s->d_scratch : nullptr, insert, s->stream);
+}
+
+// ---- many edits in one rebuild
+
+// every refusal of rt_scene_splice_ranges that needs no device, and the sorted rows; *empty: nothing to do
+static int ranges_arguments(const rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims, const char *who,
+                            SplicePlan &plan, bool *empty) {
+    const std::string w = who;
+    *empty = false;
+    uint32_t at = 0;
+    const int k = splice_plan(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, edits, num_edits, prims, plan, &at);
+    const std::string edit = ": edit " + std::to_string(at);
+    if (k == kSpliceNull) return fail(RT_ERR_INVALID, w + (edits || !num_edits ? edit + ": null records" : ": null edits"));
+    if (k == kSpliceLight) return fail(RT_ERR_INVALID, w + edit + ": first = 0 (primitive 0 is the light and stays)");
+    if (k == kSpliceSameFirst) return fail(RT_ERR_INVALID, w + edit + ": the same first as another edit (their order would be ambiguous)");
+    if (k == kSpliceOverlap) return fail(RT_ERR_INVALID, w + edit + ": its removed range overlaps another edit's");
+    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
+    if (k == kSpliceRange) return fail(RT_ERR_INVALID, w + edit + ": range outside the primitives");
+    if (k == kSpliceOk && plan.rows.empty()) {
+        *empty = true;
+        return RT_OK;
+    }
+    const int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
+    if (k == kSpliceKind) return fail(RT_ERR_INVALID, w + ": primitive " + std::to_string(at) + " is not a triangle");
+    if (k == kSpliceMany) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 primitives");
+    return RT_OK;
+}
+
+int rt_scene_splice_ranges(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims_dev, void *stream) {
+    const char *who = "rt_scene_splice_ranges";
+    Rebuilt t;
+    try {
+        SplicePlan plan;
+        bool empty = false;
+        int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty);
+        if (rc != RT_OK || empty) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        RefitState &R = s->refit;
+        std::vector<uint8_t> pinfo = splice_types(R.pinfo, plan);
+        std::vector<uint32_t> indices(plan.n_new, 0u);
+        rc = splice_ranges(R, records_of(s), plan.rows.data(), (uint32_t)plan.rows.size(), plan.n_new, plan.total_insert, prims_dev,
+                           s->num_materials, (hipStream_t)stream, t);
+        if (rc != RT_OK) return rc;
+        swap_in_splice(s, t, pinfo, indices);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        free_rebuilt(t);
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_splice_ranges_host(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims) {
+    try {
+        SplicePlan plan;
+        bool empty = false;
+        int rc = ranges_arguments(s, edits, num_edits, prims, "rt_scene_splice_ranges_host", plan, &empty);
+        if (rc != RT_OK || empty) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        const size_t bytes = sizeof(rt_prim) * (size_t)plan.total_insert;
+        if (bytes) {
+            HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+            if ((rc = grow(&s->d_scratch, &s->scratch_bytes, bytes)) != RT_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(s->d_scratch, prims, bytes, hipMemcpyHostToDevice, s->stream));
+        }
+        return rt_scene_splice_ranges(s, edits, num_edits, bytes ? (const rt_prim *)s->d_scratch : nullptr, s->stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_scene_splice_ranges_host: ") + e.what());
+    }
+}
+
+static int compact_arguments(const rt_scene *s, const uint8_t *keep, const char *who) {
+    const std::string w = who;
+    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
+    if (!keep) return fail(RT_ERR_INVALID, w + ": null mask");
+    const int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
+    return RT_OK;
+}
+
+int rt_scene_compact_triangles(rt_scene *s, const uint8_t *keep_dev, void *stream) {
+    const char *who = "rt_scene_compact_triangles";
+    int rc = compact_arguments(s, keep_dev, who);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    Rebuilt t;
+    try {
+        RefitState &R = s->refit;
+        std::vector<uint8_t> keep;
+        uint32_t n = 0;
+        if ((rc = splice_mask(R, records_of(s), keep_dev, (hipStream_t)stream, keep, &n, t)) != RT_OK || n == s->num_prims) return rc;
+        std::vector<uint8_t> pinfo;
+        pinfo.reserve(n);
+        for (uint32_t i = 0; i < s->num_prims; ++i)
+            if (keep[i]) pinfo.push_back(R.pinfo[i]);
+        std::vector<uint32_t> indices(n, 0u);
+        swap_in_splice(s, t, pinfo, indices);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        free_rebuilt(t);
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_compact_triangles_host(rt_scene *s, const uint8_t *keep) {
+    int rc = compact_arguments(s, keep, "rt_scene_compact_triangles_host");
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, s->num_prims)) != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_scratch, keep, s->num_prims, hipMemcpyHostToDevice, s->stream));
+    return rt_scene_compact_triangles(s, (const uint8_t *)s->d_scratch, s->stream);
 }
 
 int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {

@@ -174,5 +174,15 @@ struct SpliceEdit {
 // cen of `out`) and builds its tree (build_tree) on `st`; blocks.  Nothing of the scene is written,
 // and after any error nothing is left allocated.
 int splice(RefitState &R, const SceneRecords &S, const SpliceEdit &E, hipStream_t st, Rebuilt &out);
+// rt_scene_splice_ranges: the same for many edits at once.  rows: HOST, the sorted table of splice_plan
+// (rt_splice.h); recs_dev: DEVICE, total_insert records, every edit's back to back in the caller's order
+struct SpliceRow;
+int splice_ranges(RefitState &R, const SceneRecords &S, const SpliceRow *rows, uint32_t num_rows, uint32_t n_new, uint32_t total_insert,
+                  const rt_prim *recs_dev, uint32_t num_materials, hipStream_t st, Rebuilt &out);
+// rt_scene_compact_triangles: the primitives i with keep_dev[i] != 0 (DEVICE, num_prims bytes) stay.
+// Checks the mask (RT_ERR_INVALID), counts the survivors into *n_new and downloads the mask into `keep`;
+// where all stay, that is all it does and `out` stays empty.  Else as splice.
+int splice_mask(RefitState &R, const SceneRecords &S, const uint8_t *keep_dev, hipStream_t st, std::vector<uint8_t> &keep, uint32_t *n_new,
+                Rebuilt &out);
 
 }  // namespace rt

@@ -1,9 +1,12 @@
 // rt_splice.h -- the per-lane text of rt_scene_splice_triangles: the step in front of
 // the GPU builder (rt_build.h) that forms the new id space when triangles leave and enter a scene.
 //
+// and of the batched edits rt_scene_splice_ranges and rt_scene_compact_triangles (below).
+//
 // One text for gfx950 and for the host, like rt_update.h and under the same -ffp-contract=off: the
 // kernels of rt_splice.hip supply the lane index, a stand-alone host program runs the same lines in a
-// loop (tests/cpp/splice_host.cpp).  No std:: algorithm.
+// loop (tests/cpp/splice_host.cpp, splice_many_host.cpp).  No std:: algorithm in what a lane runs; the
+// host's sorting of a batched call's edits (splice_plan) is marked as such.
 //
 // The edit removes ids [first, first + remove) and puts `insert` new triangles at id `first`.  The
 // map from a new id j to where it comes from is closed-form, so no table travels:
@@ -13,7 +16,10 @@
 // Everything is written in id order (slot = id) into fresh arrays: the builder then reads them with
 // the identity as its old slot map, and its permute_slots puts the records into the new leaf order.
 #pragma once
-#include "rt_update.h"
+#include <algorithm>
+#include <vector>
+
+#include "rt_build.h"
 
 namespace rt {
 
@@ -51,15 +57,20 @@ RT_HD bool splice_ok(const SpliceArgs &A, uint32_t i) {
     return p.type == RT_TRIANGLE && p.material >= 0 && (uint32_t)p.material < A.num_materials && tri_ok(p.v);
 }
 
-// New id j.  A kept primitive copies its shading record, its centroid, its slot box and its leaf-slot
-// record; the id is word q[0].w of every kind's record (tri_record, prim_record) and nothing else in
-// any record depends on it -- a cube's or a quad's side-table index is its rank among cubes and quads,
-// which triangles coming and going do not change.  An inserted triangle is written by the encoders
-// that scene creation runs (pack_shade, pack_slots, pack_nodes and mark_sticky of rt_scene_pack.cpp).
-RT_HD void splice_gather(const SpliceArgs &A, uint32_t j) {
+// Where a new id comes from, as one word: an old id, or kSpliceNew | the index of an inserted record
+// (ids stay below 2^24, so the top bit is free).
+constexpr uint32_t kSpliceNew = 0x80000000u;
+
+// New id j from source word w.  A kept primitive copies its shading record, its centroid, its slot box
+// and its leaf-slot record; the id is word q[0].w of every kind's record (tri_record, prim_record) and
+// nothing else in any record depends on it -- a cube's or a quad's side-table index is its rank among
+// cubes and quads, which triangles coming and going do not change.  An inserted triangle is written by
+// the encoders that scene creation runs (pack_shade, pack_slots, pack_nodes and mark_sticky of
+// rt_scene_pack.cpp).
+RT_HD void splice_put(const SpliceArgs &A, uint32_t j, uint32_t w) {
     float4 q[3], b[2], s[2], c;
-    if (j >= A.first && j < A.first + A.insert) {
-        const rt_prim p = A.recs[j - A.first];
+    if (w & kSpliceNew) {
+        const rt_prim p = A.recs[w & ~kSpliceNew];
         const f3 N = tri_normal(p.v);
         s[0] = make_float4(N.x, N.y, N.z, ibits(p.material));
         s[1] = make_float4(ubits((uint32_t)RT_TRIANGLE), 0, 0, 0);
@@ -69,7 +80,7 @@ RT_HD void splice_gather(const SpliceArgs &A, uint32_t j) {
         slot_box(mn, mx, tri_sliver(p.v, A.sliver_lim), b);
         c = tri_centroid(p.v);
     } else {
-        const uint32_t o = j < A.first ? j : j - A.insert + A.remove;
+        const uint32_t o = w;
         const uint32_t slot = A.old_slot_of[o];
         for (int k = 0; k < 2; ++k) s[k] = A.old_shade[2 * (size_t)o + k];
         c = A.old_cen[o];
@@ -82,6 +93,163 @@ RT_HD void splice_gather(const SpliceArgs &A, uint32_t j) {
     for (int k = 0; k < 2; ++k) A.box[2 * (size_t)j + k] = b[k];
     for (int k = 0; k < 3; ++k) A.prims[3 * (size_t)j + k] = q[k];
     A.ident[j] = j;
+}
+// the single range: the source word in closed form (the map at the top)
+RT_HD void splice_gather(const SpliceArgs &A, uint32_t j) {
+    const bool in = j >= A.first && j < A.first + A.insert;
+    splice_put(A, j, in ? kSpliceNew | (j - A.first) : j < A.first ? j : j - A.insert + A.remove);
+}
+
+// ---- many edits in one rebuild: rt_scene_splice_ranges and rt_scene_compact_triangles.
+// Both fill one source word per new id (src) and then run the one gather over them; they differ only
+// in how the words come to be.
+// The records of a batched call stand back to back in A.recs and get one pass of splice_ok.
+RT_HD void splice_gather_src(const SpliceArgs &A, const uint32_t *src, uint32_t j) { splice_put(A, j, src[j]); }
+
+// -- the ranges route.  One row per non-empty edit, sorted by `first`: the new id where its inserted
+// records start, its old range, and where its records start in the caller's array.  Between two rows
+// the kept primitives run on: new id start + insert is old id first + remove.
+struct SpliceRow { uint32_t start, first, remove, insert, offset; };
+// the source word of new id j: the last row whose start is <= j by binary search.  Two rows share a
+// start only where the earlier one inserts nothing and the later one begins where it ends, and then the
+// earlier one owns no new id.
+RT_HD uint32_t splice_source(const SpliceRow *rows, uint32_t num_rows, uint32_t j) {
+    uint32_t lo = 0, hi = num_rows;   // rows [0, lo) start at or before j, rows [hi, num_rows) after it
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if (rows[mid].start <= j) lo = mid + 1u; else hi = mid;
+    }
+    if (lo == 0) return j;   // before the first edit
+    const SpliceRow r = rows[lo - 1u];
+    const uint32_t k = j - r.start;
+    return k < r.insert ? kSpliceNew | (r.offset + k) : r.first + r.remove + (k - r.insert);
+}
+
+// The host's part of the ranges route, shared by the library and the stand-alone program: the refusals
+// that need neither the device nor the records' contents, and the rows.  Per edit in the caller's order
+// what splice_range refuses; then, over the non-empty edits sorted by first, the same first twice and
+// overlapping removed ranges.  Without a scene (ptype null) the checks that need none still run, so
+// that they come first for every caller.  *where: the edit (caller's index) or the primitive refused.
+enum { kSpliceSameFirst = kSpliceKind + 1, kSpliceOverlap, kSpliceMany };
+struct SplicePlan {
+    std::vector<SpliceRow> rows;
+    uint32_t n_new = 0, total_insert = 0;
+};
+inline int splice_plan(uint32_t num_prims, const uint8_t *ptype, const rt_tri_edit *edits, uint32_t num_edits, const void *recs,
+                       SplicePlan &out, uint32_t *where) {
+    out = SplicePlan();
+    if (num_edits && !edits) return kSpliceNull;
+    uint64_t offset = 0;
+    std::vector<SpliceRow> rows;
+    for (uint32_t e = 0; e < num_edits; ++e) {
+        const rt_tri_edit &x = edits[e];
+        *where = e;
+        if (x.first == 0) return kSpliceLight;
+        if (x.insert && !recs) return kSpliceNull;
+        if (x.remove == 0 && x.insert == 0) continue;
+        if (offset + x.insert >= (1u << 24)) return kSpliceMany;
+        rows.push_back(SpliceRow{e, x.first, x.remove, x.insert, (uint32_t)offset});   // start: the caller's index for now
+        offset += x.insert;
+    }
+    std::sort(rows.begin(), rows.end(), [](const SpliceRow &a, const SpliceRow &b) { return a.first < b.first || (a.first == b.first && a.start < b.start); });
+    for (size_t k = 1; k < rows.size(); ++k) {
+        *where = rows[k].start;
+        if (rows[k - 1].first == rows[k].first) return kSpliceSameFirst;
+        if ((uint64_t)rows[k - 1].first + rows[k - 1].remove > rows[k].first) return kSpliceOverlap;
+    }
+    if (!ptype) return kSpliceRange;   // no scene: every range is outside it
+    for (const SpliceRow &r : rows) {
+        *where = r.start;
+        if ((uint64_t)r.first + r.remove > num_prims) return kSpliceRange;
+    }
+    for (const SpliceRow &r : rows)
+        for (uint32_t id = r.first; id < r.first + r.remove; ++id)
+            if ((ptype[id] & 0x7f) != RT_TRIANGLE) { *where = id; return kSpliceKind; }
+    int64_t shift = 0;   // new id minus old id at the row's first
+    for (SpliceRow &r : rows) {
+        r.start = (uint32_t)((int64_t)r.first + shift);
+        shift += (int64_t)r.insert - (int64_t)r.remove;
+    }
+    if ((int64_t)num_prims + shift >= (int64_t)(1u << 24)) return kSpliceMany;
+    out.rows.swap(rows);
+    out.n_new = (uint32_t)((int64_t)num_prims + shift);
+    out.total_insert = (uint32_t)offset;
+    return kSpliceOk;
+}
+// the type bytes of the new id space (RefitState::pinfo) from the rows
+inline std::vector<uint8_t> splice_types(const std::vector<uint8_t> &ptype, const SplicePlan &plan) {
+    std::vector<uint8_t> out;
+    out.reserve(plan.n_new);
+    uint32_t at = 0;
+    for (const SpliceRow &r : plan.rows) {
+        out.insert(out.end(), ptype.begin() + at, ptype.begin() + r.first);
+        out.insert(out.end(), r.insert, (uint8_t)RT_TRIANGLE);
+        at = r.first + r.remove;
+    }
+    out.insert(out.end(), ptype.begin() + at, ptype.end());
+    return out;
+}
+
+// -- the mask route.  keep[i] != 0: old id i stays; survivors keep their order, so the new id of a
+// survivor is the number of survivors before it -- an exclusive prefix count of the flags -- and
+// src[that] = i.  A workgroup takes kMaskGroup consecutive old ids, every lane a run of consecutive ids
+// of them (one id per lane on the device, the whole group for the host's one lane).  Nothing is handed
+// from one workgroup to another inside a launch: mask_count writes a count per group, mask_top turns
+// the counts into the groups' first new ids (one workgroup, as many counts at a time as it has lanes,
+// with a running carry: no size is too large for it), mask_scatter writes the source words.
+constexpr uint32_t kMaskGroup = 256;
+struct MaskArgs {
+    uint32_t n;                 // old primitives
+    const uint8_t *keep;
+    const float4 *old_shade;    // word [2 i + 1].x: the type of old id i, as the kernels read it
+    uint32_t *sums;             // mask_groups(n) + 1 words: per group its count, then its first new id; last: the survivors
+    uint32_t *src;
+};
+RT_HD uint32_t mask_groups(uint32_t n) { return (n + kMaskGroup - 1u) / kMaskGroup; }
+// the mask drops neither primitive 0 nor anything but a triangle
+RT_HD bool mask_ok(const MaskArgs &M, uint32_t i) {
+    return M.keep[i] != 0 || (i != 0 && fbits(M.old_shade[2 * (size_t)i + 1].x) == (uint32_t)RT_TRIANGLE);
+}
+// the ids [r0, r1) of group g that lane tid of `stride` takes (stride divides kMaskGroup)
+RT_HD void mask_run(uint32_t n, uint32_t g, uint32_t tid, uint32_t stride, uint32_t &r0, uint32_t &r1) {
+    const uint32_t per = kMaskGroup / stride, a = g * kMaskGroup + tid * per;
+    r0 = a < n ? a : n;
+    r1 = a + per < n ? a + per : n;
+}
+// survivors in the lane's run, and before it in the group (scan: stride words); total: the group's
+template <class P>
+RT_HD uint32_t mask_before(const MaskArgs &M, uint32_t g, uint32_t *scan, uint32_t &total, P &par) {
+    uint32_t r0, r1, c = 0;
+    mask_run(M.n, g, par.tid, par.stride, r0, r1);
+    for (uint32_t i = r0; i < r1; ++i) c += M.keep[i] != 0;
+    return wg_scan(scan, c, total, par);
+}
+template <class P>
+RT_HD void mask_count(const MaskArgs &M, uint32_t g, uint32_t *scan, P &par) {
+    uint32_t total;
+    mask_before(M, g, scan, total, par);
+    if (par.tid == 0) M.sums[g] = total;
+}
+template <class P>
+RT_HD void mask_top(const MaskArgs &M, uint32_t *scan, P &par) {
+    const uint32_t ng = mask_groups(M.n);
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < ng; base += par.stride) {
+        const uint32_t g = base + par.tid, v = g < ng ? M.sums[g] : 0u;
+        uint32_t total;
+        const uint32_t before = wg_scan(scan, v, total, par);
+        if (g < ng) M.sums[g] = carry + before;
+        carry += total;
+    }
+    if (par.tid == 0) M.sums[ng] = carry;
+}
+template <class P>
+RT_HD void mask_scatter(const MaskArgs &M, uint32_t g, uint32_t *scan, P &par) {
+    uint32_t r0, r1, total;
+    uint32_t at = M.sums[g] + mask_before(M, g, scan, total, par);
+    mask_run(M.n, g, par.tid, par.stride, r0, r1);
+    for (uint32_t i = r0; i < r1; ++i)
+        if (M.keep[i] != 0) M.src[at++] = i;
 }
 
 }  // namespace rt

@@ -359,6 +359,42 @@ int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, cons
                               void *stream);
 /* the same with the records in host memory (staged on the scene's private stream) */
 int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert);
+/* Several such edits in ONE rebuild.  edits: HOST memory, in any order; every `first` is an id of the
+ * OLD id space.  prims_dev: DEVICE rt_prim, the inserted records of all edits back to back in the
+ * order of `edits` (not in sorted order).  The result is the old list with every range
+ * [first, first + remove) erased and that edit's records put in its place -- what the edits give when
+ * applied one at a time through rt_scene_splice_triangles in descending order of `first`.  Contract,
+ * blocking and what stays valid are rt_scene_splice_triangles' word for word; the caller's ids behind
+ * an edit shift by the sum of insert - remove of the edits before them.  Adjacent ranges
+ * (first2 == first1 + remove1) are fine.  Edits with remove == 0 && insert == 0 are skipped (but still
+ * refused for first == 0); with no edit left the call is RT_OK and launches nothing.  No limit on
+ * num_edits but memory.
+ *   RT_ERR_INVALID      checked on the host before any HIP call: null scene, null edits with
+ *                       num_edits > 0, null records with any insert > 0; per edit first == 0, a range
+ *                       outside the primitives, a non-triangle in a removed range; two non-empty edits
+ *                       with the same `first` (their order in the result would be ambiguous) or whose
+ *                       removed ranges overlap.  Checked on the device in one pass over all records,
+ *                       before anything is allocated or written: a record that is no RT_TRIANGLE,
+ *                       a material outside [0, num_materials), a NaN / infinite vertex;
+ *   RT_ERR_UNSUPPORTED, RT_ERR_HIP  as for rt_scene_splice_triangles.
+ * After every refusal the scene is untouched. */
+typedef struct { uint32_t first, remove, insert; } rt_tri_edit;
+int rt_scene_splice_ranges(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims_dev, void *stream);
+/* the same with the records in host memory (staged on the scene's private stream) */
+int rt_scene_splice_ranges_host(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims);
+/* Drop triangles by a keep-mask decided on the GPU, in one rebuild.  keep_dev: DEVICE memory,
+ * num_prims bytes indexed by old id; primitive i stays where keep_dev[i] != 0.  Survivors keep their
+ * relative order: the new id of a survivor is the number of survivors before it (an exclusive prefix
+ * count on the GPU; the ranges never travel through the host).  Contract, blocking and what stays
+ * valid are rt_scene_splice_triangles'.  The survivor count is read back; a mask that keeps everything
+ * is RT_OK and does nothing further -- nothing is rebuilt, a ready refit schedule stays ready.
+ *   RT_ERR_INVALID      null scene or mask; a mask that drops primitive 0 or any non-triangle
+ *                       (checked on the GPU in a pass of its own before anything is written);
+ *   RT_ERR_UNSUPPORTED, RT_ERR_HIP  as for rt_scene_splice_triangles.
+ * After every refusal the scene is untouched.  Nothing enters through this call. */
+int rt_scene_compact_triangles(rt_scene *s, const uint8_t *keep_dev, void *stream);
+/* the same with the mask in host memory (staged on the scene's private stream) */
+int rt_scene_compact_triangles_host(rt_scene *s, const uint8_t *keep);
 /* rt_bvh_cost of the scene's CURRENT device tree -- the node records as they are after any number of
  * updates, rebuilds and splices -- reduced on the GPU (per workgroup, then over the workgroups' partial
  * sums; no copy of the tree to the host).  Blocks like rt_renderer_tile_work: runs on `stream` and

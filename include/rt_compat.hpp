@@ -314,6 +314,21 @@ class Scene {   // template/scene.h:37
     void SpliceTrianglesDevice(uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert, void *stream = nullptr) {
         rt_check(rt_scene_splice_triangles(handle(), first, remove, prims_dev, insert, stream));
     }
+    // Several such edits in one rebuild: every `first` is an id of the scene as it is now, the edits in any
+    // order, their records (host memory) back to back in the order of `edits`
+    void SpliceRanges(const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims) {
+        rt_check(rt_scene_splice_ranges_host(handle(), edits, num_edits, prims));
+    }
+    void SpliceRangesDevice(const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims_dev, void *stream = nullptr) {
+        rt_check(rt_scene_splice_ranges(handle(), edits, num_edits, prims_dev, stream));
+    }
+    // Triangles dropped by a keep-mask in DEVICE memory (one byte per primitive, != 0 stays), as a GPU
+    // culling or destruction pass leaves it; compacted and rebuilt on the GPU in one call
+    void CompactTriangles(const uint8_t *keep_dev, void *stream = nullptr) {
+        rt_check(rt_scene_compact_triangles(handle(), keep_dev, stream));
+    }
+    // the same with the mask in host memory
+    void CompactTrianglesHost(const uint8_t *keep) { rt_check(rt_scene_compact_triangles_host(handle(), keep)); }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
