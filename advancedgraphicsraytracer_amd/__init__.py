@@ -60,6 +60,12 @@ class TriEdit(C.Structure):
     _fields_ = [("first", C.c_uint32), ("remove", C.c_uint32), ("insert", C.c_uint32)]
 
 
+class PrimEdit(C.Structure):
+    """rt_prim_edit (rt_tri_edit's layout): primitives [first, first + remove) of any kind leave, `insert`
+    records of any kind enter at `first`"""
+    _fields_ = TriEdit._fields_
+
+
 class Material(C.Structure):
     _fields_ = [("kind", C.c_int32), ("color", C.c_float * 3), ("color2", C.c_float * 3), ("ior", C.c_float),
                 ("diffuse", C.c_float), ("texture", C.c_int32)]
@@ -167,6 +173,12 @@ def lib():
         "rt_scene_splice_ranges_host": ([vp, C.POINTER(TriEdit), u32, C.POINTER(Prim)], C.c_int),
         "rt_scene_compact_triangles": ([vp, vp, vp], C.c_int),
         "rt_scene_compact_triangles_host": ([vp, vp], C.c_int),
+        "rt_scene_splice_prims": ([vp, C.POINTER(PrimEdit), u32, vp, vp, vp], C.c_int),
+        "rt_scene_splice_prims_host": ([vp, C.POINTER(PrimEdit), u32, C.POINTER(Prim), fp], C.c_int),
+        "rt_scene_compact_prims": ([vp, vp, vp], C.c_int),
+        "rt_scene_compact_prims_host": ([vp, vp], C.c_int),
+        "rt_scene_set_prim_materials": ([vp, u32, u32, vp, vp], C.c_int),
+        "rt_scene_set_prim_materials_host": ([vp, u32, u32, C.POINTER(i32)], C.c_int),
         "rt_sbvh_build_host": ([C.POINTER(Prim), C.POINTER(C.c_float), u32, C.POINTER(vp), C.POINTER(C.POINTER(u32)),
                                 C.POINTER(SceneInfo)], C.c_int),
         "rt_image_load": ([C.c_char_p, C.POINTER(C.POINTER(u32)), C.POINTER(u32), C.POINTER(u32)], C.c_int),
@@ -795,6 +807,92 @@ class Scene:
         if k.size != n:
             raise RTError(RT_ERR_INVALID, "compact_triangles: keep must be num_prims flags")
         _check(self.L.rt_scene_compact_triangles_host(self.h, k.ctypes.data_as(C.c_void_p)))
+
+    def splice_prims(self, edits, stream=None):
+        """rt_scene_splice_prims: splice_ranges with primitives of any kind.  edits: a list of
+        (first, remove, prims) in any order, every `first` an id of the scene as it is now; prims a list of
+        sphere() / plane() / cube() / quad() / triangle() records (staged by the library), each cube's
+        and quad's .T its transform.  Or a list of (first, remove, recs, insert) where `recs` of any one
+        edit (None in the others) is a pair of torch tensors on the scene's device in pack_prims' layout
+        -- (records [total, 11] 32-bit words, transforms [total, 16] float32 or None) -- holding every
+        edit's records back to back in the order of `edits`, and `insert` each edit's record count.  A
+        type change is remove 1, insert 1 at the same first.  Primitive 0 stays.  Afterwards the scene
+        equals a fresh one created from the edited list.  Blocks; render the next frame with reset=True."""
+        torch = _torch()
+        edits = [tuple(e) for e in edits]
+        arr = (PrimEdit * max(len(edits), 1))()
+        if edits and all(len(e) == 4 for e in edits):
+            recs = [e[2] for e in edits if e[2] is not None]
+            total = sum(int(e[3]) for e in edits)
+            if any(r is not recs[0] for r in recs) or (total and not recs):
+                raise RTError(RT_ERR_INVALID, "splice_prims: one pair of tensors holds the records of all edits")
+            rec, T = (recs[0] if isinstance(recs[0], (tuple, list)) else (recs[0], None)) if recs else (None, None)
+            if rec is not None:
+                if not isinstance(rec, torch.Tensor) or not rec.is_cuda or rec.device.index != self.device:
+                    raise RTError(RT_ERR_INVALID, "splice_prims: the records must be a tensor on the scene's device")
+                if rec.element_size() != 4 or rec.dim() != 2 or rec.shape[1] != 11 or rec.shape[0] != total:
+                    raise RTError(RT_ERR_INVALID, "splice_prims: records must be [sum of the counts, 11] 32-bit words")
+                rec = rec.contiguous()
+            if T is not None:
+                if not isinstance(T, torch.Tensor) or not T.is_cuda or T.device.index != self.device:
+                    raise RTError(RT_ERR_INVALID, "splice_prims: the transforms must be a tensor on the scene's device")
+                T = T.to(dtype=torch.float32).contiguous().reshape(-1, 16)
+                if T.shape[0] != total:
+                    raise RTError(RT_ERR_INVALID, "splice_prims: one transform per record")
+            for k, (f, n, _, m) in enumerate(edits):
+                arr[k].first, arr[k].remove, arr[k].insert = int(f), int(n), int(m)
+            s = stream if stream is not None else torch.cuda.current_stream(f"cuda:{self.device}").cuda_stream
+            _check(self.L.rt_scene_splice_prims(self.h, arr, len(edits), C.c_void_p(rec.data_ptr()) if total else None,
+                                                C.c_void_p(T.data_ptr()) if total and T is not None else None, C.c_void_p(s)))
+            return
+        prims = []
+        for k, (f, n, new) in enumerate(edits):
+            if isinstance(new, torch.Tensor) or (len(new) == 2 and isinstance(new[0], torch.Tensor)):
+                raise RTError(RT_ERR_INVALID, "splice_prims: with tensors every edit is (first, remove, recs, insert)")
+            new = list(new)
+            arr[k].first, arr[k].remove, arr[k].insert = int(f), int(n), len(new)
+            prims += new
+        recs = (Prim * len(prims))(*prims) if prims else None
+        T = _transforms(prims) if prims else None
+        _check(self.L.rt_scene_splice_prims_host(self.h, arr, len(edits), recs, None if T is None else _fptr(T)))
+
+    def compact_prims(self, keep, stream=None):
+        """rt_scene_compact_prims: compact_triangles without the kind restriction -- primitive i of any
+        kind stays where keep[i] != 0, never dropping primitive 0.  keep: as compact_triangles takes it."""
+        torch = _torch()
+        n = self.info["num_prims"]
+        if isinstance(keep, torch.Tensor):
+            if not keep.is_cuda or keep.device.index != self.device:
+                raise RTError(RT_ERR_INVALID, "compact_prims: the tensor must be on the scene's device")
+            if keep.dtype not in (torch.uint8, torch.bool) or keep.numel() != n:
+                raise RTError(RT_ERR_INVALID, "compact_prims: keep must be num_prims uint8 flags")
+            k = keep.contiguous()
+            s = stream if stream is not None else torch.cuda.current_stream(k.device).cuda_stream
+            _check(self.L.rt_scene_compact_prims(self.h, C.c_void_p(k.data_ptr()), C.c_void_p(s)))
+            return
+        k = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+        if k.size != n:
+            raise RTError(RT_ERR_INVALID, "compact_prims: keep must be num_prims flags")
+        _check(self.L.rt_scene_compact_prims_host(self.h, k.ctypes.data_as(C.c_void_p)))
+
+    def set_prim_materials(self, first, materials, stream=None):
+        """rt_scene_set_prim_materials: the materials of primitives [first, first + len(materials)) become
+        `materials` -- a sequence / numpy array of material indices (staged by the library) or an int32
+        torch tensor on the scene's device.  In place: no rebuild, no refit, a ready refit schedule stays
+        ready.  Not the light's (first >= 1).  Blocks; render the next frame with reset=True."""
+        torch = _torch()
+        if isinstance(materials, torch.Tensor):
+            if not materials.is_cuda or materials.device.index != self.device:
+                raise RTError(RT_ERR_INVALID, "set_prim_materials: the tensor must be on the scene's device")
+            if materials.dtype != torch.int32:
+                raise RTError(RT_ERR_INVALID, "set_prim_materials: materials must be int32")
+            m = materials.contiguous().reshape(-1)
+            s = stream if stream is not None else torch.cuda.current_stream(m.device).cuda_stream
+            _check(self.L.rt_scene_set_prim_materials(self.h, first, m.numel(), C.c_void_p(m.data_ptr()) if m.numel() else None,
+                                                      C.c_void_p(s)))
+            return
+        m = np.ascontiguousarray(materials, np.int32).reshape(-1)
+        _check(self.L.rt_scene_set_prim_materials_host(self.h, first, m.size, m.ctypes.data_as(C.POINTER(C.c_int32))))
 
     def IntersectBVH(self, rays, stream=None):
         """Batched Scene::IntersectBVH.  rays: (n,7) [O, D, tmax] numpy or torch.

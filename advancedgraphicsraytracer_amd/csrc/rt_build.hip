@@ -170,7 +170,7 @@ int run_build(const BuildArgs &B, hipStream_t st, const std::string &who, Rebuil
 }  // namespace
 
 void free_rebuilt(Rebuilt &r) {
-    for (void **p : {&r.nodes, &r.prims, &r.slot_box, &r.slot_of, &r.index, &r.shade, &r.cen}) {
+    for (void **p : {&r.nodes, &r.prims, &r.slot_box, &r.slot_of, &r.index, &r.shade, &r.cen, &r.xprims}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }

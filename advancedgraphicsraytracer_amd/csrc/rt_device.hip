@@ -62,6 +62,8 @@ struct rt_scene {
                                 // is checked at rt_scene_create)
     int walk = RT_WALK_LANE;    // camera-ray walk of the global-node primary+shadow kernel
     bool ext = false;           // needs the kext kernels (cubes, quads, textures, non-Light light)
+    bool ext_fixed = false;     // ... for reasons no edit of the primitives changes (family_fixed): kept for
+                                // the commit of rt_scene_splice_prims, which takes ext anew by creation's rule
     bool pt_lanes = true;           // levels >= 1 run the lane state machine (RT_PT_LANES=0: k_pt_level)
     bool pt_dynamic = true;         // wavefront levels >= 1 fetch chunks dynamically (RT_PT_DYNAMIC=0: static)
     bool pt_wavefront = true;   // depth >= 2 path tracing: wavefront (k_pt_level) vs one kernel (k_render)
@@ -361,10 +363,12 @@ int scene_create(const rt_scene_desc *d, rt_scene **out) {
     s->num_prims = d->num_prims;
     s->num_materials = d->num_materials;
     s->ext = p.ext;
+    s->ext_fixed = p.ext_fixed;
     s->has_cubes = p.has_cubes;
     s->refit.boxes_finite = p.boxes_finite;
     s->quads = s->quad_lanes = p.has_quads;
     s->refit.sliver_lim = o.sliver_lim;
+    s->refit.sticky_spheres = o.sticky_spheres;
     rc = upload(&s->d_nodes, p.nodes);
     if (rc == RT_OK) rc = upload(&s->d_prims, p.prims);
     if (rc == RT_OK) rc = upload(&s->d_shade, p.shade);
@@ -1783,12 +1787,13 @@ int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove,
 // ---- many edits in one rebuild
 
 // every refusal of rt_scene_splice_ranges that needs no device, and the sorted rows; *empty: nothing to do
+// (any_kind: rt_scene_splice_prims, the same refusals but the kind's)
 static int ranges_arguments(const rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims, const char *who,
-                            SplicePlan &plan, bool *empty) {
+                            SplicePlan &plan, bool *empty, bool any_kind = false) {
     const std::string w = who;
     *empty = false;
     uint32_t at = 0;
-    const int k = splice_plan(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, edits, num_edits, prims, plan, &at);
+    const int k = splice_plan(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, edits, num_edits, prims, plan, &at, any_kind);
     const std::string edit = ": edit " + std::to_string(at);
     if (k == kSpliceNull) return fail(RT_ERR_INVALID, w + (edits || !num_edits ? edit + ": null records" : ": null edits"));
     if (k == kSpliceLight) return fail(RT_ERR_INVALID, w + edit + ": first = 0 (primitive 0 is the light and stays)");
@@ -1892,6 +1897,146 @@ int rt_scene_compact_triangles_host(rt_scene *s, const uint8_t *keep) {
     if ((rc = grow(&s->d_scratch, &s->scratch_bytes, s->num_prims)) != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(s->d_scratch, keep, s->num_prims, hipMemcpyHostToDevice, s->stream));
     return rt_scene_compact_triangles(s, (const uint8_t *)s->d_scratch, s->stream);
+}
+
+// ---- primitives of any kind enter and leave: the batched routes with the kind restriction
+// lifted, and the material word alone
+
+// the commit's own share: the new side table, and the kernel family by the rule creation uses
+// (kernel_family).  A scene that gained its first cube no longer admits the wave walk: the camera-walk
+// policy falls back as rt_scene_set_camera_walk would refuse it now.  The renderers read s->ext, s->walk
+// and the view per frame, so one created before the edit takes the new family with its next frame.
+static void swap_in_kinds(rt_scene *s, Rebuilt &t) {
+    if (s->d_xprims) (void)hipFree(s->d_xprims);
+    s->d_xprims = t.xprims;
+    t.xprims = nullptr;
+    s->view.xprims = (const float4 *)s->d_xprims;
+    const std::vector<uint8_t> &types = s->refit.pinfo;
+    kernel_family(s->num_prims, [&types](uint32_t i) { return types[i] & 0x7f; }, s->ext_fixed, s->ext, s->has_cubes);
+    if (s->has_cubes && s->walk != RT_WALK_LANE) s->walk = RT_WALK_LANE;
+}
+
+int rt_scene_splice_prims(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims_dev,
+                          const float *transforms_dev, void *stream) {
+    const char *who = "rt_scene_splice_prims";
+    Rebuilt t;
+    try {
+        SplicePlan plan;
+        bool empty = false;
+        int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty, true);
+        if (rc != RT_OK || empty) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        RefitState &R = s->refit;
+        SpliceKinds K;
+        K.T_dev = transforms_dev;
+        std::vector<uint32_t> indices(plan.n_new, 0u);
+        rc = splice_ranges(R, records_of(s), plan.rows.data(), (uint32_t)plan.rows.size(), plan.n_new, plan.total_insert, prims_dev,
+                           s->num_materials, (hipStream_t)stream, t, &K);
+        if (rc != RT_OK) return rc;
+        swap_in_splice(s, t, K.types, indices);
+        swap_in_kinds(s, t);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        free_rebuilt(t);
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_splice_prims_host(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims,
+                               const float *transforms) {
+    try {
+        SplicePlan plan;
+        bool empty = false;
+        int rc = ranges_arguments(s, edits, num_edits, prims, "rt_scene_splice_prims_host", plan, &empty, true);
+        if (rc != RT_OK || empty) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        const size_t count = plan.total_insert;
+        const size_t pbytes = (sizeof(rt_prim) * count + 15u) & ~(size_t)15u, tbytes = transforms ? 64 * count : 0;
+        char *base = nullptr;
+        if (count) {
+            HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+            if ((rc = grow(&s->d_scratch, &s->scratch_bytes, pbytes + tbytes)) != RT_OK) return rc;
+            base = (char *)s->d_scratch;
+            HIP_TRY(hipMemcpyAsync(base, prims, sizeof(rt_prim) * count, hipMemcpyHostToDevice, s->stream));
+            if (tbytes) HIP_TRY(hipMemcpyAsync(base + pbytes, transforms, tbytes, hipMemcpyHostToDevice, s->stream));
+        }
+        return rt_scene_splice_prims(s, edits, num_edits, (const rt_prim *)base, tbytes ? (const float *)(base + pbytes) : nullptr,
+                                     s->stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string("rt_scene_splice_prims_host: ") + e.what());
+    }
+}
+
+int rt_scene_compact_prims(rt_scene *s, const uint8_t *keep_dev, void *stream) {
+    const char *who = "rt_scene_compact_prims";
+    int rc = compact_arguments(s, keep_dev, who);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    Rebuilt t;
+    try {
+        std::vector<uint8_t> keep;
+        uint32_t n = 0;
+        SpliceKinds K;
+        if ((rc = splice_mask(s->refit, records_of(s), keep_dev, (hipStream_t)stream, keep, &n, t, &K)) != RT_OK || n == s->num_prims)
+            return rc;
+        std::vector<uint32_t> indices(n, 0u);
+        swap_in_splice(s, t, K.types, indices);
+        swap_in_kinds(s, t);
+        return RT_OK;
+    } catch (const std::exception &e) {
+        free_rebuilt(t);
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_compact_prims_host(rt_scene *s, const uint8_t *keep) {
+    int rc = compact_arguments(s, keep, "rt_scene_compact_prims_host");
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, s->num_prims)) != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_scratch, keep, s->num_prims, hipMemcpyHostToDevice, s->stream));
+    return rt_scene_compact_prims(s, (const uint8_t *)s->d_scratch, s->stream);
+}
+
+// every refusal of rt_scene_set_prim_materials that needs no device; *empty: nothing to do
+static int materials_arguments(const rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials, const char *who, bool *empty) {
+    const std::string w = who;
+    *empty = false;
+    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
+    if (count == 0) {
+        *empty = true;
+        return RT_OK;
+    }
+    if (!materials) return fail(RT_ERR_INVALID, w + ": null materials");
+    // the light's material feeds SceneView::light_mat and the kernel family
+    if (first == 0) return fail(RT_ERR_INVALID, w + ": the range holds primitive 0 (the light's material stays)");
+    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, w + ": range outside the primitives");
+    return RT_OK;
+}
+
+int rt_scene_set_prim_materials(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials_dev, void *stream) {
+    const char *who = "rt_scene_set_prim_materials";
+    bool empty = false;
+    int rc = materials_arguments(s, first, count, materials_dev, who, &empty);
+    if (rc != RT_OK || empty) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return set_materials(s->refit, records_of(s), first, count, materials_dev, s->num_materials, (hipStream_t)stream);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_set_prim_materials_host(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials) {
+    bool empty = false;
+    int rc = materials_arguments(s, first, count, materials, "rt_scene_set_prim_materials_host", &empty);
+    if (rc != RT_OK || empty) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
+    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, sizeof(int32_t) * (size_t)count)) != RT_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_scratch, materials, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s->stream));
+    return rt_scene_set_prim_materials(s, first, count, (const int32_t *)s->d_scratch, s->stream);
 }
 
 int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {

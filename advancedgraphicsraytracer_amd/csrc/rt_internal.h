@@ -68,7 +68,29 @@ struct ScenePack {            // everything scene_create computes before it touc
     std::vector<float> pcen;  // ... and its centroid (3 floats), what a rebuild bins by
     uint32_t stack_depth;     // LDS stack entries per lane
     bool ext, has_cubes, nested, walk_fits, boxes_finite, has_quads;
+    bool ext_fixed;           // ext for reasons no edit of the primitives changes (family_fixed)
 };
+// The kernel family a scene needs, one rule for creation (check_description) and for the commit of an
+// edit that lets kinds enter and leave (rt_scene_splice_prims).  ext: the kext kernels -- a cube or a
+// quad anywhere (the light included), or `fixed`: a light material other than the core four, a texture
+// material.  has_cubes: cube acceptance depends on the visiting order, no wave walk.
+// type_of(i): the type of primitive i.
+inline bool family_fixed(const rt_material *mats, uint32_t num_materials, int32_t light_material) {
+    const int lk = mats[light_material].kind;
+    bool fixed = !(lk == RT_LIGHT || lk == RT_DIFFUSE || lk == RT_MIRROR || lk == RT_DSMIX);
+    for (uint32_t i = 0; i < num_materials && !fixed; ++i) fixed = mats[i].kind == RT_TEXTURE;
+    return fixed;
+}
+template <class TypeOf>
+inline void kernel_family(uint32_t n, TypeOf type_of, bool fixed, bool &ext, bool &has_cubes) {
+    ext = fixed;
+    has_cubes = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        const int t = type_of(i);
+        if (t == RT_CUBE) has_cubes = true;
+        if (t == RT_CUBE || t == RT_QUAD) ext = true;
+    }
+}
 int pack_scene(const rt_scene_desc *d, const PackOptions &o, ScenePack &out);
 // what follows from a tree's depth: the LDS stack entries per lane, and whether the wave walk's word
 // stack fits beside the lane stacks (take_tree; rt_scene_rebuild)

@@ -62,6 +62,8 @@ struct RefitState {
     std::vector<float> pbox;
     std::vector<float> pcen;        // and its centroid (3 floats): what a rebuild bins by (rt_build.h)
     double sliver_lim = 0.0;        // mark_sticky's sine limit at creation (RT_WALK_STICKY)
+    bool sticky_spheres = true;     // ... and its rule for spheres and quads (RT_WALK_STICKY_SPHERES): both are
+                                    // read at creation only, and an inserted record is marked by them
     bool boxes_finite = true;       // every primitive box was finite at creation
     bool state_ready = false;       // slot_of, slot_box and cen are on the device (and authoritative from there on)
     bool refit_ready = false;       // ... and so is the schedule of the current topology
@@ -75,6 +77,8 @@ struct RefitState {
     bool bvh_stale = false;         // the device boxes are newer than the host tree (rt_scene_copy_bvh downloads them)
     void *d_ranges = nullptr;       // rt_scene_transform_triangles' range table (first, prefix counts, matrices)
     size_t ranges_bytes = 0;
+    void *d_types = nullptr;        // rt_scene_splice_prims' check: the inserted records' type bytes, kept between calls
+    size_t types_bytes = 0;
 };
 void free_refit(RefitState &R);
 
@@ -143,6 +147,7 @@ int ensure_state(RefitState &R, const SceneRecords &S);
 struct Rebuilt {
     void *nodes = nullptr, *prims = nullptr, *slot_box = nullptr, *slot_of = nullptr, *index = nullptr;
     void *shade = nullptr, *cen = nullptr;   // a splice's new id space (rt_splice.hip); a rebuild leaves them null
+    void *xprims = nullptr;                  // ... and its side table, where kinds entered or left (null: the scene's stays)
     uint32_t nodes_used = 0, depth = 0, max_leaf = 0, root_word = 0;
     bool finite = false;
     uint32_t stats[4] = {0, 0, 0, 0};
@@ -176,13 +181,28 @@ struct SpliceEdit {
 int splice(RefitState &R, const SceneRecords &S, const SpliceEdit &E, hipStream_t st, Rebuilt &out);
 // rt_scene_splice_ranges: the same for many edits at once.  rows: HOST, the sorted table of splice_plan
 // (rt_splice.h); recs_dev: DEVICE, total_insert records, every edit's back to back in the caller's order
+// K (below) non-null: rt_scene_splice_prims, records of any kind.
 struct SpliceRow;
+struct SpliceKinds;
 int splice_ranges(RefitState &R, const SceneRecords &S, const SpliceRow *rows, uint32_t num_rows, uint32_t n_new, uint32_t total_insert,
-                  const rt_prim *recs_dev, uint32_t num_materials, hipStream_t st, Rebuilt &out);
+                  const rt_prim *recs_dev, uint32_t num_materials, hipStream_t st, Rebuilt &out, SpliceKinds *K = nullptr);
 // rt_scene_compact_triangles: the primitives i with keep_dev[i] != 0 (DEVICE, num_prims bytes) stay.
 // Checks the mask (RT_ERR_INVALID), counts the survivors into *n_new and downloads the mask into `keep`;
 // where all stay, that is all it does and `out` stays empty.  Else as splice.
+// K non-null: rt_scene_compact_prims, anything but primitive 0 may leave.
 int splice_mask(RefitState &R, const SceneRecords &S, const uint8_t *keep_dev, hipStream_t st, std::vector<uint8_t> &keep, uint32_t *n_new,
-                Rebuilt &out);
+                Rebuilt &out, SpliceKinds *K = nullptr);
+// Primitives of every kind through the two routes above: the check admits the five kinds,
+// the side-table ranks of the new id space are counted, and the gather writes a new side table
+// (Rebuilt::xprims).  In: one mat4 per inserted record on the DEVICE (null: identity).  Out: the type
+// bytes of the new id space, from which the caller takes RefitState::pinfo and the kernel family.
+struct SpliceKinds {
+    const float *T_dev = nullptr;
+    std::vector<uint8_t> types;
+};
+// rt_scene_set_prim_materials: checks mats_dev[0 .. count) against num_materials in a pass of its own
+// (RT_ERR_INVALID, nothing written), then writes the material words of [first, first + count).  Blocks.
+int set_materials(RefitState &R, const SceneRecords &S, uint32_t first, uint32_t count, const int32_t *mats_dev, uint32_t num_materials,
+                  hipStream_t st);
 
 }  // namespace rt

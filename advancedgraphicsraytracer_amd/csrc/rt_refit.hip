@@ -156,11 +156,12 @@ int prepare_updates(RefitState &R, const SceneRecords &S, hipStream_t st) {
 
 void free_refit(RefitState &R) {
     R.state_ready = false;
-    for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp, &R.d_flag, &R.d_ranges, &R.d_cen, &R.d_index}) {
+    for (void **p : {&R.d_slot_of, &R.d_slot_box, &R.d_list, &R.d_lvl, &R.d_grp, &R.d_flag, &R.d_ranges, &R.d_cen, &R.d_index, &R.d_types}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     R.ranges_bytes = 0;
+    R.types_bytes = 0;
     R.refit_ready = false;
     R.plan_info = PlanInfo{};
 }

@@ -158,13 +158,8 @@ int check_description(const rt_scene_desc *d, ScenePack &s) {
         if (!d->textures[i].pixels || !d->textures[i].width || !d->textures[i].height)
             return fail(RT_ERR_INVALID, "texture " + std::to_string(i) + " is empty");
     // needs the kext kernels: cubes, quads, textures, a light material other than the core four
-    s.ext = d->prims[0].type == RT_QUAD;
-    {
-        const int lk = d->materials[d->prims[0].material].kind;
-        s.ext = s.ext || !(lk == RT_LIGHT || lk == RT_DIFFUSE || lk == RT_MIRROR || lk == RT_DSMIX);
-    }
-    for (uint32_t i = 0; i < n && !s.ext; ++i) s.ext = d->prims[i].type == RT_CUBE || d->prims[i].type == RT_QUAD;
-    for (uint32_t i = 0; i < d->num_materials && !s.ext; ++i) s.ext = d->materials[i].kind == RT_TEXTURE;
+    s.ext_fixed = family_fixed(d->materials, d->num_materials, d->prims[0].material);
+    kernel_family(n, [d](uint32_t i) { return d->prims[i].type; }, s.ext_fixed, s.ext, s.has_cubes);
     if (d->sky_pixels) {
         uint32_t w = d->sky_width, h = d->sky_height;
         if (!w || !h || (w & (w - 1)) || (h & (h - 1)))
@@ -263,11 +258,9 @@ void pack_nodes(const rt_scene_desc *d, const PackOptions &o, const std::vector<
 void pack_xprims(const rt_scene_desc *d, ScenePack &s, std::vector<uint32_t> &xindex) {
     std::vector<float4> &xprims = s.xprims;
     xindex.assign(d->num_prims, 0);
-    s.has_cubes = false;
     for (uint32_t id = 0; id < d->num_prims; ++id) {
         const rt_prim &p = d->prims[id];
-        if (p.type != RT_CUBE && p.type != RT_QUAD) continue;
-        if (p.type == RT_CUBE) s.has_cubes = true;
+        if (p.type != RT_CUBE && p.type != RT_QUAD) continue;   // has_cubes: kernel_family's (check_description)
         PrimX x;
         prim_transform(p, transform_of(d, id), x);
         xindex[id] = (uint32_t)(xprims.size() / 8);

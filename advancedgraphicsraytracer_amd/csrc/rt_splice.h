@@ -1,7 +1,9 @@
 // rt_splice.h -- the per-lane text of rt_scene_splice_triangles: the step in front of
 // the GPU builder (rt_build.h) that forms the new id space when triangles leave and enter a scene.
 //
-// and of the batched edits rt_scene_splice_ranges and rt_scene_compact_triangles (below).
+// and of the batched edits rt_scene_splice_ranges and rt_scene_compact_triangles (below),
+// and of rt_scene_splice_prims, rt_scene_compact_prims and rt_scene_set_prim_materials (at
+// the end): the same routes with every kind of primitive, and a side table that follows them.
 //
 // One text for gfx950 and for the host, like rt_update.h and under the same -ffp-contract=off: the
 // kernels of rt_splice.hip supply the lane index, a stand-alone host program runs the same lines in a
@@ -36,6 +38,15 @@ struct SpliceArgs {
     uint32_t *ident;
     // ... and what the scene keeps as it is written here (shading record, centroid)
     float4 *shade, *cen;
+    // primitives of every kind (all null / unread on the triangle routes): one mat4 per
+    // inserted record (null: identity), mark_sticky's rule for spheres and quads, the side table as it
+    // is, per new id its side-table index (null: kept cubes and quads keep theirs, the identity map),
+    // and the new side table
+    const float *T;
+    bool sticky_spheres;
+    const float4 *old_xprims;
+    const uint32_t *xrank;
+    float4 *xprims;
 };
 
 // The refusals that need neither the device nor the records' contents, in the order the header lists
@@ -61,24 +72,37 @@ RT_HD bool splice_ok(const SpliceArgs &A, uint32_t i) {
 // (ids stay below 2^24, so the top bit is free).
 constexpr uint32_t kSpliceNew = 0x80000000u;
 
+// mark_sticky's rule per kind (rt_scene_pack.cpp): a sliver triangle, a sphere or a quad where the scene
+// was created with sticky spheres, never a plane or a cube
+RT_HD bool splice_sticky(const SpliceArgs &A, const rt_prim &p) {
+    if (p.type == RT_SPHERE || p.type == RT_QUAD) return A.sticky_spheres;
+    return p.type == RT_TRIANGLE && tri_sliver(p.v, A.sliver_lim);
+}
+RT_HD bool has_xentry(uint32_t type) { return type == (uint32_t)RT_CUBE || type == (uint32_t)RT_QUAD; }
+
 // New id j from source word w.  A kept primitive copies its shading record, its centroid, its slot box
-// and its leaf-slot record; the id is word q[0].w of every kind's record (tri_record, prim_record) and
-// nothing else in any record depends on it -- a cube's or a quad's side-table index is its rank among
-// cubes and quads, which triangles coming and going do not change.  An inserted triangle is written by
-// the encoders that scene creation runs (pack_shade, pack_slots, pack_nodes and mark_sticky of
-// rt_scene_pack.cpp).
+// and its leaf-slot record; the id is word q[0].w of every kind's record (tri_record, prim_record).  A
+// cube's or a quad's side-table index is its rank among cubes and quads: triangles coming and going do
+// not change it (xrank null), any other kind coming or going does, and then the kept entry moves from
+// its old index to xrank[j] and the two words that hold the index -- s[1].z of the shading record,
+// q[1].x of the leaf-slot record -- follow.  An inserted record is written by the encoders that scene
+// creation runs (pack_shade, pack_slots, pack_xprims, pack_nodes and mark_sticky of rt_scene_pack.cpp).
 RT_HD void splice_put(const SpliceArgs &A, uint32_t j, uint32_t w) {
     float4 q[3], b[2], s[2], c;
     if (w & kSpliceNew) {
-        const rt_prim p = A.recs[w & ~kSpliceNew];
-        const f3 N = tri_normal(p.v);
-        s[0] = make_float4(N.x, N.y, N.z, ibits(p.material));
-        s[1] = make_float4(ubits((uint32_t)RT_TRIANGLE), 0, 0, 0);
-        tri_record(p.v, j, q);
-        f3 mn, mx;
-        tri_box(p.v, mn, mx);
-        slot_box(mn, mx, tri_sliver(p.v, A.sliver_lim), b);
-        c = tri_centroid(p.v);
+        const uint32_t i = w & ~kSpliceNew;
+        const rt_prim p = A.recs[i];
+        const bool side = has_xentry((uint32_t)p.type);
+        const uint32_t xi = side && A.xrank ? A.xrank[j] : 0u;
+        PrimX x;
+        PrimGeom g;
+        prim_transform(p, side && A.T ? A.T + 16u * (size_t)i : nullptr, x);
+        prim_geometry(p, x, g);
+        prim_shade(p, x, xi, s);
+        prim_record(p, x, j, xi, q);
+        if (side) prim_xentry(p, x, A.xprims + 8 * (size_t)xi);
+        slot_box(g.bmin, g.bmax, splice_sticky(A, p), b);
+        c = make_float4(g.centroid.x, g.centroid.y, g.centroid.z, 0.0f);
     } else {
         const uint32_t o = w;
         const uint32_t slot = A.old_slot_of[o];
@@ -87,6 +111,12 @@ RT_HD void splice_put(const SpliceArgs &A, uint32_t j, uint32_t w) {
         for (int k = 0; k < 2; ++k) b[k] = A.old_box[2 * (size_t)slot + k];
         for (int k = 0; k < 3; ++k) q[k] = A.old_prims[3 * (size_t)slot + k];
         q[0].w = ibits((int)j);
+        if (A.xrank && has_xentry(fbits(s[1].x))) {
+            const uint32_t xo = fbits(s[1].z), xn = A.xrank[j];
+            for (int k = 0; k < 8; ++k) A.xprims[8 * (size_t)xn + k] = A.old_xprims[8 * (size_t)xo + k];
+            s[1].z = ubits(xn);
+            q[1].x = ubits(xn);
+        }
     }
     for (int k = 0; k < 2; ++k) A.shade[2 * (size_t)j + k] = s[k];
     A.cen[j] = c;
@@ -135,8 +165,9 @@ struct SplicePlan {
     std::vector<SpliceRow> rows;
     uint32_t n_new = 0, total_insert = 0;
 };
+// any_kind: rt_scene_splice_prims, whose removed ranges may hold any kind.
 inline int splice_plan(uint32_t num_prims, const uint8_t *ptype, const rt_tri_edit *edits, uint32_t num_edits, const void *recs,
-                       SplicePlan &out, uint32_t *where) {
+                       SplicePlan &out, uint32_t *where, bool any_kind = false) {
     out = SplicePlan();
     if (num_edits && !edits) return kSpliceNull;
     uint64_t offset = 0;
@@ -163,7 +194,7 @@ inline int splice_plan(uint32_t num_prims, const uint8_t *ptype, const rt_tri_ed
         if ((uint64_t)r.first + r.remove > num_prims) return kSpliceRange;
     }
     for (const SpliceRow &r : rows)
-        for (uint32_t id = r.first; id < r.first + r.remove; ++id)
+        for (uint32_t id = r.first; id < r.first + r.remove && !any_kind; ++id)
             if ((ptype[id] & 0x7f) != RT_TRIANGLE) { *where = id; return kSpliceKind; }
     int64_t shift = 0;   // new id minus old id at the row's first
     for (SpliceRow &r : rows) {
@@ -176,14 +207,16 @@ inline int splice_plan(uint32_t num_prims, const uint8_t *ptype, const rt_tri_ed
     out.total_insert = (uint32_t)offset;
     return kSpliceOk;
 }
-// the type bytes of the new id space (RefitState::pinfo) from the rows
-inline std::vector<uint8_t> splice_types(const std::vector<uint8_t> &ptype, const SplicePlan &plan) {
+// the type bytes of the new id space (RefitState::pinfo) from the rows; rec_types: per inserted record
+// its type as the check wrote it (null: triangles all)
+inline std::vector<uint8_t> splice_types(const std::vector<uint8_t> &ptype, const SplicePlan &plan, const uint8_t *rec_types = nullptr) {
     std::vector<uint8_t> out;
     out.reserve(plan.n_new);
     uint32_t at = 0;
     for (const SpliceRow &r : plan.rows) {
         out.insert(out.end(), ptype.begin() + at, ptype.begin() + r.first);
-        out.insert(out.end(), r.insert, (uint8_t)RT_TRIANGLE);
+        if (rec_types) out.insert(out.end(), rec_types + r.offset, rec_types + r.offset + r.insert);
+        else out.insert(out.end(), r.insert, (uint8_t)RT_TRIANGLE);
         at = r.first + r.remove;
     }
     out.insert(out.end(), ptype.begin() + at, ptype.end());
@@ -251,5 +284,54 @@ RT_HD void mask_scatter(const MaskArgs &M, uint32_t g, uint32_t *scan, P &par) {
     for (uint32_t i = r0; i < r1; ++i)
         if (M.keep[i] != 0) M.src[at++] = i;
 }
+
+// ---- primitives of every kind: rt_scene_splice_prims and rt_scene_compact_prims take the
+// two routes above -- source words, one gather -- with three additions: a check that admits all five
+// kinds, the side-table ranks of the new id space, and a gather that moves the side table (splice_put).
+
+// an inserted record: one of the five kinds, one of the scene's materials, and prim_fields_ok -- PrimRecs::ok
+// without its "as the scene holds them" test.  The lane also leaves the record's type byte for the host,
+// which splices RefitState::pinfo from it without a copy of the records
+RT_HD bool splice_prim_ok(const SpliceArgs &A, uint32_t i, uint8_t *types) {
+    const rt_prim p = A.recs[i];
+    types[i] = (uint8_t)p.type;
+    if (p.type < RT_SPHERE || p.type > RT_TRIANGLE) return false;
+    if (p.material < 0 || (uint32_t)p.material >= A.num_materials) return false;
+    return prim_fields_ok(p, A.T && has_xentry((uint32_t)p.type) ? A.T + 16u * (size_t)i : nullptr);
+}
+// the mask drops anything but primitive 0
+RT_HD bool mask_prims_ok(const MaskArgs &M, uint32_t i) { return M.keep[i] != 0 || i != 0; }
+
+// Side-table ranks.  The new side-table index of new id j is the number of cubes and quads among the new
+// ids below j -- an exclusive prefix count of a per-new-id flag, which is the mask route's count with
+// the flag in the place of keep: rank_flag writes the flags (from the source word: the old shading
+// record's type word, or the inserted record's type), mask_count and mask_top run over them unchanged
+// (MaskArgs{n_new, flags, ..}), and mask_ranks, mask_scatter's sibling, writes every id's count-before
+// instead of the survivors' ids.  sums[mask_groups(n_new)] is the new side table's size.
+RT_HD void rank_flag(const SpliceArgs &A, const uint32_t *src, uint8_t *flags, uint32_t j) {
+    const uint32_t w = src[j];
+    const uint32_t type = w & kSpliceNew ? (uint32_t)A.recs[w & ~kSpliceNew].type : fbits(A.old_shade[2 * (size_t)w + 1].x);
+    flags[j] = has_xentry(type) ? 1 : 0;
+}
+template <class P>
+RT_HD void mask_ranks(const MaskArgs &M, uint32_t g, uint32_t *scan, uint32_t *rank, P &par) {
+    uint32_t r0, r1, total;
+    uint32_t at = M.sums[g] + mask_before(M, g, scan, total, par);
+    mask_run(M.n, g, par.tid, par.stride, r0, r1);
+    for (uint32_t i = r0; i < r1; ++i) {
+        rank[i] = at;
+        at += M.keep[i] != 0;
+    }
+}
+
+// ---- rt_scene_set_prim_materials: the material word of the shading records of [first, first + count),
+// nothing else; the check is a pass of its own
+struct MatArgs {
+    uint32_t first, count, num_materials;
+    const int32_t *mats;
+    float4 *shade;
+};
+RT_HD bool mats_ok(const MatArgs &M, uint32_t i) { return M.mats[i] >= 0 && (uint32_t)M.mats[i] < M.num_materials; }
+RT_HD void mats_put(const MatArgs &M, uint32_t i) { M.shade[2 * (size_t)(M.first + i)].w = ibits(M.mats[i]); }
 
 }  // namespace rt

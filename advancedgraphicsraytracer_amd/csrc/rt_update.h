@@ -106,6 +106,21 @@ struct TriXform {
     }
 };
 
+// a record of one of the five kinds: every field the kind reads finite, its transform Ti finite
+// where one is read (null: none), its box finite.  The rule rt_scene_update_prims and
+// rt_scene_splice_prims (rt_splice.h) share
+RT_HD bool prim_fields_ok(const rt_prim &p, const float *Ti) {
+    bool ok = true;
+    const int nf = p.type == RT_TRIANGLE ? 9 : p.type == RT_CUBE ? 6 : p.type == RT_QUAD ? 1 : 4;
+    for (int k = 0; k < nf; ++k) ok = ok && finite_f(p.v[k]);
+    for (int k = 0; Ti && k < 16; ++k) ok = ok && finite_f(Ti[k]);
+    PrimX x;
+    PrimGeom g;
+    prim_transform(p, Ti, x);
+    prim_geometry(p, x, g);
+    return ok && finite_f3(g.bmin) && finite_f3(g.bmax);
+}
+
 // rt_scene_update_prims: record i of any kind for primitive first + i, with transform T + 16 i
 // (T may be null) where its kind reads one -- cubes and quads
 struct PrimRecs {
@@ -122,16 +137,7 @@ struct PrimRecs {
         const rt_prim p = prims[i];
         if ((uint32_t)p.type != fbits(A.shade[2 * (size_t)id + 1].x) || (uint32_t)p.material != fbits(A.shade[2 * (size_t)id].w))
             return false;
-        bool ok = true;
-        const int nf = p.type == RT_TRIANGLE ? 9 : p.type == RT_CUBE ? 6 : p.type == RT_QUAD ? 1 : 4;
-        for (int k = 0; k < nf; ++k) ok = ok && finite_f(p.v[k]);
-        const float *Ti = transform(p, i);
-        for (int k = 0; Ti && k < 16; ++k) ok = ok && finite_f(Ti[k]);
-        PrimX x;
-        PrimGeom g;
-        prim_transform(p, Ti, x);
-        prim_geometry(p, x, g);
-        return ok && finite_f3(g.bmin) && finite_f3(g.bmax);
+        return prim_fields_ok(p, transform(p, i));
     }
     // the leaf-slot record, the shading record (material word kept), a cube's or a quad's
     // side-table entry (through the index its shading record holds) and the slot box; the sticky

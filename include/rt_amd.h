@@ -344,7 +344,8 @@ int rt_scene_copy_update_plan(const rt_scene *s, uint32_t *list, uint32_t *lvl, 
  * Ids the caller holds for later rt_scene_update_triangles, rt_scene_transform_triangles or
  * rt_scene_update_prims calls shift with the edit: every id >= first + remove moves by
  * insert - remove.  That bookkeeping is the caller's.
- * Only triangles enter and leave; primitives of other kinds may sit anywhere, also behind the edit.
+ * Only triangles enter and leave through this call (primitives of other kinds may sit anywhere, also
+ * behind the edit); every kind does through rt_scene_splice_prims below.
  *   RT_ERR_INVALID      null scene, or null records with insert > 0; first == 0 (primitive 0 is the
  *                       light and stays); first + remove > num_prims; a non-triangle in the removed
  *                       range; an inserted record that is no RT_TRIANGLE, whose material is outside
@@ -395,6 +396,56 @@ int rt_scene_splice_ranges_host(rt_scene *s, const rt_tri_edit *edits, uint32_t 
 int rt_scene_compact_triangles(rt_scene *s, const uint8_t *keep_dev, void *stream);
 /* the same with the mask in host memory (staged on the scene's private stream) */
 int rt_scene_compact_triangles_host(rt_scene *s, const uint8_t *keep);
+/* Primitives of any kind enter and leave: rt_scene_splice_ranges with the kind restriction lifted.
+ * Edits are in old ids and in any order; a single edit is num_edits == 1.  Removed ranges may hold any
+ * kind; the inserted records, back to back in prims_dev in the order of `edits`, may be RT_SPHERE,
+ * RT_PLANE, RT_CUBE, RT_QUAD or RT_TRIANGLE.  transforms_dev: DEVICE float[16 * total insert], one mat4
+ * per inserted record, read for cubes and quads only; NULL = identity for all (rt_scene_update_prims'
+ * convention).  A type change is remove = 1, insert = 1 at the same `first`.  Primitive 0, the light,
+ * stays.
+ * The contract is rt_scene_splice_triangles', extended: afterwards the scene is bit for bit a fresh
+ * rt_scene_create of the edited description (materials, textures and sky as they were; per-primitive
+ * transforms edited alongside the primitives) in everything the kernels read and the host can ask for --
+ * nodes (sticky words included), the primitive-index array, leaf-slot records with the new ids and the
+ * new side-table indices, shading records, the cubes' and quads' side table in its new rank order, slot
+ * boxes, centroids, root word, stack depth, walk eligibility, and the kernel family: a scene that gains
+ * its first cube or quad renders with the kernels such a scene needs, one that loses its last returns
+ * to the core ones.  Where the new scene no longer admits the wave walk (a cube entered), the camera-
+ * walk policy falls back to RT_WALK_LANE, as rt_scene_set_camera_walk would refuse RT_WALK_WAVE now; it
+ * is not raised again when the cubes leave.  Blocks like an update; render the next frame with
+ * reset = 1; renderers stay valid and keep their buffers; the next in-place update rebuilds its refit
+ * schedule, and rt_scene_update_prims then addresses the new ids.
+ *   RT_ERR_INVALID      checked on the host before any HIP call: null scene, null edits with
+ *                       num_edits > 0, null records with any insert > 0; per edit first == 0, a range
+ *                       outside the primitives; two non-empty edits with the same `first` or whose
+ *                       removed ranges overlap.  Checked on the device in one pass over all records,
+ *                       before anything of the scene is written: a type outside the five kinds, a
+ *                       material outside [0, num_materials), a NaN / infinite field that the kind
+ *                       reads, a NaN / infinite transform where one is read, a NaN / infinite box --
+ *                       rt_scene_update_prims' rules without "same type and material as the scene";
+ *   RT_ERR_UNSUPPORTED, RT_ERR_HIP  as for rt_scene_splice_triangles.
+ * After every refusal the scene is untouched. */
+typedef rt_tri_edit rt_prim_edit;   /* { uint32_t first, remove, insert; } */
+int rt_scene_splice_prims(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims_dev,
+                          const float *transforms_dev, void *stream);
+/* the same with records and transforms in host memory (staged on the scene's private stream) */
+int rt_scene_splice_prims_host(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims,
+                               const float *transforms);
+/* rt_scene_compact_triangles without the kind restriction: the mask may drop anything but primitive 0.
+ * A mask that keeps everything still does nothing.  Contract as rt_scene_splice_prims. */
+int rt_scene_compact_prims(rt_scene *s, const uint8_t *keep_dev, void *stream);
+int rt_scene_compact_prims_host(rt_scene *s, const uint8_t *keep);
+/* Materials change in place: the material of primitive first + i becomes materials_dev[i] (DEVICE
+ * int32[count]).  No rebuild, no refit, a ready refit schedule stays ready; rt_scene_update_prims
+ * checks its records against the new materials afterwards.  Blocks like an update; render the next
+ * frame with reset = 1.  count == 0 is RT_OK.
+ *   RT_ERR_INVALID      null scene or materials; a range that holds primitive 0 (the light's material
+ *                       feeds the light sampling and the kernel family) or lies outside the
+ *                       primitives; a material outside [0, num_materials), checked on the device in a
+ *                       pass of its own before anything is written.
+ * After every refusal the scene is untouched. */
+int rt_scene_set_prim_materials(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials_dev, void *stream);
+int rt_scene_set_prim_materials_host(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials);
 /* rt_bvh_cost of the scene's CURRENT device tree -- the node records as they are after any number of
  * updates, rebuilds and splices -- reduced on the GPU (per workgroup, then over the workgroups' partial
  * sums; no copy of the tree to the host).  Blocks like rt_renderer_tile_work: runs on `stream` and

@@ -329,6 +329,26 @@ class Scene {   // template/scene.h:37
     }
     // the same with the mask in host memory
     void CompactTrianglesHost(const uint8_t *keep) { rt_check(rt_scene_compact_triangles_host(handle(), keep)); }
+    // Primitives of any kind enter and leave (a projectile sphere, a crate, a sphere that becomes a cube:
+    // remove 1, insert 1): SpliceRanges without the kind restriction.  transforms: one mat4 (16 floats) per
+    // inserted record, read for cubes and quads; null = identity.  Primitive 0, the light, stays
+    void SplicePrims(const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims, const float *transforms = nullptr) {
+        rt_check(rt_scene_splice_prims_host(handle(), edits, num_edits, prims, transforms));
+    }
+    void SplicePrimsDevice(const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims_dev, const float *transforms_dev = nullptr,
+                           void *stream = nullptr) {
+        rt_check(rt_scene_splice_prims(handle(), edits, num_edits, prims_dev, transforms_dev, stream));
+    }
+    // CompactTriangles without the kind restriction: anything but primitive 0 may leave
+    void CompactPrims(const uint8_t *keep_dev, void *stream = nullptr) { rt_check(rt_scene_compact_prims(handle(), keep_dev, stream)); }
+    void CompactPrimsHost(const uint8_t *keep) { rt_check(rt_scene_compact_prims_host(handle(), keep)); }
+    // The materials of primitives [first, first + count) (not the light's), in place: no rebuild, no refit
+    void SetPrimMaterials(uint32_t first, uint32_t count, const int32_t *materials) {
+        rt_check(rt_scene_set_prim_materials_host(handle(), first, count, materials));
+    }
+    void SetPrimMaterialsDevice(uint32_t first, uint32_t count, const int32_t *materials_dev, void *stream = nullptr) {
+        rt_check(rt_scene_set_prim_materials(handle(), first, count, materials_dev, stream));
+    }
     float3 GetLightColor() const { return float3(24, 24, 22); }          // template/scene.h:237-239
     float3 GetLightDir() const { return float3(0.0f, -1.0f, 0.0f); }     // template/scene.h:240-242
     rt_scene_info Info() { rt_scene_info i{}; rt_check(rt_scene_get_info(handle(), &i)); return i; }
