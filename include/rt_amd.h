@@ -243,7 +243,8 @@ int rt_scene_copy_bvh(const rt_scene *s, void *nodes, uint32_t *indices);
  * the scene's device (renderers run frames on their own streams), runs on `stream`, and returns when
  * the scene is ready for any stream.  The caller renders the next frame with reset = 1, as the
  * reference does (renderer.cpp:237).  Renderers keep their timed choices, tile orders and deals
- * (speed only; frames are identical under any of them), and the scene keeps its camera-walk policy.
+ * (speed only; tests/test_edits_under_schedule_gpu.py holds the frames of a warm renderer after every
+ * kind of edit to those of one without any such state), and the scene keeps its camera-walk policy.
  * The first update of a scene builds its refit schedule on the GPU, unless rt_scene_prepare_updates
  * did so at a moment of the caller's choosing.
  *   RT_ERR_INVALID      null pointer, range outside the primitives, a non-triangle primitive in the
