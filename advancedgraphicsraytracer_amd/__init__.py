@@ -96,6 +96,11 @@ class BvhCost(C.Structure):
                 ("max_leaf", C.c_uint32)]
 
 
+class UpdateStatus(C.Structure):
+    """rt_update_status"""
+    _fields_ = [(n, C.c_uint64) for n in ("submitted", "applied", "refused", "first_refused")]
+
+
 class Camera(C.Structure):
     """Camera state (camera.h:93-100)."""
     _fields_ = [("pos", C.c_float * 3), ("top_left", C.c_float * 3), ("top_right", C.c_float * 3),
@@ -160,6 +165,10 @@ def lib():
         "rt_scene_update_prims": ([vp, u32, u32, vp, vp, vp], C.c_int),
         "rt_scene_update_prims_host": ([vp, u32, u32, C.POINTER(Prim), fp], C.c_int),
         "rt_scene_transform_triangles": ([vp, C.POINTER(TriXform), u32, vp, vp], C.c_int),
+        "rt_scene_update_triangles_async": ([vp, u32, u32, vp, vp, C.POINTER(C.c_uint64)], C.c_int),
+        "rt_scene_update_prims_async": ([vp, u32, u32, vp, vp, vp, C.POINTER(C.c_uint64)], C.c_int),
+        "rt_scene_transform_triangles_async": ([vp, C.POINTER(TriXform), u32, vp, vp, C.POINTER(C.c_uint64)], C.c_int),
+        "rt_scene_update_sync": ([vp, C.POINTER(UpdateStatus)], C.c_int),
         "rt_scene_rebuild": ([vp, vp], C.c_int),
         "rt_scene_rebuild_stats": ([vp, C.POINTER(C.c_uint32)], C.c_int),
         "rt_scene_prepare_updates": ([vp, vp], C.c_int),
@@ -604,6 +613,9 @@ class Scene:
     def close(self):
         h = getattr(self, "h", None)
         if h is not None and h.value:
+            if getattr(self, "_pending", None):
+                self.L.rt_scene_update_sync(h, None)   # the queued updates still read the tensors held here
+                self._pending = []
             self.L.rt_scene_destroy(h)
             self.h = None
 
@@ -623,30 +635,63 @@ class Scene:
                                         idx.ctypes.data_as(C.POINTER(C.c_uint32))))
         return nodes, idx
 
-    def update_triangles(self, first, verts, stream=None):
+    def _enqueued(self, ticket, *tensors):
+        """a stream-ordered update reads `tensors` when it runs: held until update_sync"""
+        if ticket.value:
+            if getattr(self, "_pending", None) is None:
+                self._pending = []
+            self._pending.append(tensors)
+        return int(ticket.value)
+
+    def update_sync(self):
+        """rt_scene_update_sync: waits for every update enqueued with wait=False, drops the tensors
+        held for them and returns {"submitted", "applied", "refused", "first_refused", "refusal"}:
+        first_refused is the ticket of the earliest refusal since the previous sync (0: none) and
+        refusal what rt_last_error says of it (None: none)."""
+        st = UpdateStatus()
+        _check(self.L.rt_scene_update_sync(self.h, C.byref(st)))
+        self._pending = []
+        out = {n: int(getattr(st, n)) for n, _ in UpdateStatus._fields_}
+        out["refusal"] = self.L.rt_last_error().decode(errors="replace") if st.first_refused else None
+        return out
+
+    def update_triangles(self, first, verts, stream=None, wait=True):
         """rt_scene_update_triangles: new vertices for triangle primitives [first, first + count) and an
         in-place BVH refit.  verts: [count, 9] (or [count, 3, 3]) float32, A, B, C per triangle -- a torch
         tensor on the scene's device, or a numpy array (staged by the library).  Blocks until the scene
-        is ready; render the next frame with reset=True."""
+        is ready; render the next frame with reset=True.
+        wait=False (rt_scene_update_triangles_async): enqueued on `stream` without any host wait; needs
+        a device tensor, returns the update's ticket, and the outcome shows at update_sync()."""
         torch = _torch()
+        if not wait and not (isinstance(verts, torch.Tensor) and verts.is_cuda):
+            raise RTError(RT_ERR_INVALID, "update_triangles: wait=False needs a device tensor")
         if isinstance(verts, torch.Tensor) and verts.is_cuda:
             if verts.device.index != self.device:
                 raise RTError(RT_ERR_INVALID, "update_triangles: vertices on another device than the scene")
             v = verts.to(dtype=torch.float32).contiguous().reshape(-1, 9)
             s = stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
+            if not wait:
+                t = C.c_uint64(0)
+                _check(self.L.rt_scene_update_triangles_async(self.h, first, v.shape[0], C.c_void_p(v.data_ptr()), C.c_void_p(s),
+                                                              C.byref(t)))
+                return self._enqueued(t, v)
             _check(self.L.rt_scene_update_triangles(self.h, first, v.shape[0], C.c_void_p(v.data_ptr()), C.c_void_p(s)))
             return
         v = np.ascontiguousarray(verts.numpy() if isinstance(verts, torch.Tensor) else verts, np.float32).reshape(-1, 9)
         _check(self.L.rt_scene_update_triangles_host(self.h, first, len(v), _fptr(v)))
 
-    def update_prims(self, first, prims, stream=None):
+    def update_prims(self, first, prims, stream=None, wait=True):
         """rt_scene_update_prims: new records for primitives [first, first + count) of any kind (types and
         materials as the scene holds them) and an in-place BVH refit -- Primitive::UpdateTransform /
         Scene::SetTime.  prims: a list of sphere() / plane() / cube() / quad() / triangle() records, whose
         .T is honoured; or a pair of torch tensors on the scene's device, (records [count, 11] int32 or
         float32 words, transforms [count, 16] float32 or None), as pack_prims lays them out.  Moves the
-        light when the range holds primitive 0.  Blocks; render the next frame with reset=True."""
+        light when the range holds primitive 0.  Blocks; render the next frame with reset=True.
+        wait=False (rt_scene_update_prims_async): the tensor pair only, no host wait, returns the ticket;
+        a range holding primitive 0 is RT_ERR_UNSUPPORTED (the light moves through the blocking call)."""
         torch = _torch()
+        if not wait and not (isinstance(prims, (tuple, list)) and len(prims) == 2 and isinstance(prims[0], torch.Tensor)):
+            raise RTError(RT_ERR_INVALID, "update_prims: wait=False needs device tensors")
         if isinstance(prims, (tuple, list)) and len(prims) == 2 and isinstance(prims[0], torch.Tensor):
             rec, T = prims
             if not rec.is_cuda or rec.device.index != self.device or (T is not None and (not T.is_cuda or T.device.index != self.device)):
@@ -659,6 +704,11 @@ class Scene:
                 if T.shape[0] != rec.shape[0]:
                     raise RTError(RT_ERR_INVALID, "update_prims: one transform per record")
             s = stream if stream is not None else torch.cuda.current_stream(rec.device).cuda_stream
+            if not wait:
+                t = C.c_uint64(0)
+                _check(self.L.rt_scene_update_prims_async(self.h, first, rec.shape[0], C.c_void_p(rec.data_ptr()),
+                                                          None if T is None else C.c_void_p(T.data_ptr()), C.c_void_p(s), C.byref(t)))
+                return self._enqueued(t, rec, T)
             _check(self.L.rt_scene_update_prims(self.h, first, rec.shape[0], C.c_void_p(rec.data_ptr()),
                                                 None if T is None else C.c_void_p(T.data_ptr()), C.c_void_p(s)))
             return
@@ -667,13 +717,17 @@ class Scene:
         T = _transforms(prims)
         _check(self.L.rt_scene_update_prims_host(self.h, first, len(prims), arr, None if T is None else _fptr(T)))
 
-    def transform_triangles(self, ranges, rest, stream=None):
+    def transform_triangles(self, ranges, rest, stream=None, wait=True):
         """rt_scene_transform_triangles: ranges = [(first, count, M)] -- disjoint runs of triangle
         primitives, any order, each with its mat4 (16 floats) --; rest = their object-space vertices
         [total, 9] (or [total, 3, 3]) float32, the ranges back to back, a torch tensor on the scene's
         device or a numpy array (uploaded).  World vertices are TransformPosition(rest, M) as
-        mesh_to_prims computes them; one call moves every range and refits once."""
+        mesh_to_prims computes them; one call moves every range and refits once.
+        wait=False (rt_scene_transform_triangles_async): rest must be a device tensor; no host wait
+        (`ranges` is consumed before the call returns), returns the ticket."""
         torch = _torch()
+        if not wait and not (isinstance(rest, torch.Tensor) and rest.is_cuda):
+            raise RTError(RT_ERR_INVALID, "transform_triangles: wait=False needs a device tensor")
         arr = (TriXform * len(ranges))()
         for k, (f, n, M) in enumerate(ranges):
             arr[k].first, arr[k].count = int(f), int(n)
@@ -684,6 +738,11 @@ class Scene:
         if v.shape[0] != sum(int(n) for _, n, _ in ranges):
             raise RTError(RT_ERR_INVALID, "transform_triangles: rest must hold 9 floats per triangle of the ranges")
         s = stream if stream is not None else torch.cuda.current_stream(v.device).cuda_stream
+        if not wait:
+            t = C.c_uint64(0)
+            _check(self.L.rt_scene_transform_triangles_async(self.h, arr, len(ranges), C.c_void_p(v.data_ptr()), C.c_void_p(s),
+                                                             C.byref(t)))
+            return self._enqueued(t, v)
         _check(self.L.rt_scene_transform_triangles(self.h, arr, len(ranges), C.c_void_p(v.data_ptr()), C.c_void_p(s)))
 
     def rebuild(self, stream=None):

@@ -233,6 +233,14 @@ namespace {
 
 enum { kWalk, kSplit, kOverlap, kGate };   // rt_renderer::tune_ev rows
 
+// A stream that is about to read the scene waits for its stream-ordered updates: the
+// scene's one event, and only while an async update is pending -- otherwise one branch.
+inline int after_updates(const rt_scene *s, hipStream_t st) {
+    if (!s->refit.async.issued) return RT_OK;
+    HIP_TRY(hipStreamWaitEvent(st, s->refit.async.done, 0));
+    return RT_OK;
+}
+
 void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -632,6 +640,8 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
         // this frame's results buffer was last read by the finish of two frames ago
         if (pipe && !used[k] && r->pt_fin_set[par]) HIP_TRY(hipStreamWaitEvent(X, r->pt_fin[par], 0));
         if (pipe && !used[k] && tile_cost) HIP_TRY(hipStreamWaitEvent(X, r->cost_ev, 0));   // the cleared cost map
+        if (pipe && !used[k])
+            if (int rc = after_updates(s, X); rc != RT_OK) return rc;   // (serial: launch_render's wait on st)
         used[k] = true;
         char *b = static_cast<char *>(r->d_pt[k]);
         auto take = [&](size_t bytes) { char *q = b; b += (bytes + 255u) & ~(size_t)255u; return q; };
@@ -1014,6 +1024,7 @@ int work_frame(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
         HIP_TRY(hipMalloc(&r->d_work, sizeof(uint32_t) * n));
         r->work_cap = n;
     }
+    if ((rc = after_updates(s, st)) != RT_OK) return rc;
     HIP_TRY(hipMemsetAsync(r->d_work, 0, sizeof(uint32_t) * n, st));
     SceneView view = s->view;
     view.wave_primary = 0;
@@ -1272,6 +1283,9 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     F.fwd_dst = fwd_dst;
     if (F.ntiles_local == 0) return RT_OK;
     hipStream_t st = (hipStream_t)stream;
+    // the caller's stream (serial frames, the heat map, finishing passes); a renderer stream that
+    // takes the frame kernel waits too (below, launch_pt_frame)
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
     if (p->mode == RT_MODE_BVH_HEAT) {
         // The BVH heat map: the plain serial launch in the tiles' own order.  It reads none of the
         // renderer's timed choices and writes none (no parameter key, gate, walk, order or overlap
@@ -1319,6 +1333,8 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     const bool ps_ok = s->ps_pipeline != 0 && ps_kernel && !r->split_tg.active() && !F.tile_cost && !P.walk_pending &&
                        ps_bytes <= (2ull << 30);
     if (int rc = overlap_step(r, F, L, ps_ok, ps_bytes, st, P); rc != RT_OK) return rc;
+    if (L.stream != st)
+        if (int rc = after_updates(s, L.stream); rc != RT_OK) return rc;
     L.lds_bytes = stack_bytes(s) + walk_bytes(s, view);   // the camera walk's word stack when it runs
     frame_build(r, view, F, L, P.depth > 0);
     if (int rc = submit_frame(r, view, F, L, P, st); rc != RT_OK) return rc;
@@ -1458,8 +1474,25 @@ int rt_scene_create_recipe_ex(const char *name, const char *mesh_dir, int32_t de
     }
 }
 
+// What rt_scene_update_sync does, and every blocking scene entry point first: waits for the enqueued
+// async updates and folds their outcomes into the host's state.  The root of a checked refit over
+// finite primitive boxes is finite by construction, so the flags rise as after a blocking update,
+// without a read-back.  A scene without pending async updates pays one branch.
+static int fold_updates(rt_scene *s) {
+    if (!s->refit.async.issued) return RT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    uint64_t applied = 0;
+    const int rc = drain_updates(s->refit, &applied);
+    if (rc != RT_OK) return rc;
+    if (applied) {
+        s->view.bounds_finite = s->refit.boxes_finite ? 1 : 0;
+        if (s->refit.boxes_finite) s->nested = true;
+    }
+    return RT_OK;
+}
+
 int rt_scene_destroy(rt_scene *s) {
-    free_scene(s);
+    free_scene(s);   // waits for the whole device: nothing of an async update is left to fold
     return RT_OK;
 }
 
@@ -1490,6 +1523,7 @@ int rt_scene_set_camera_walk(rt_scene *s, int walk) {
 int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
     if (!cs || !nodes || !indices) return fail(RT_ERR_INVALID, "null argument");
     rt_scene *s = const_cast<rt_scene *>(cs);
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     // boxes refitted, or the whole tree rebuilt, on the device since the last copy (both block, so they are settled)
     if (s->refit.bvh_stale || s->refit.topo_stale) {
         HIP_TRY(hipSetDevice(s->device));
@@ -1541,6 +1575,7 @@ int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const
     if (rc != RT_OK) return rc;
     if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: range outside the primitives");
     if ((rc = require_triangles(s, first, count, who)) != RT_OK) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     try {
         bool finite = false;
@@ -1575,6 +1610,7 @@ int rt_scene_update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_
     int rc = refit_supported(s, who);
     if (rc != RT_OK) return rc;
     if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims: range outside the primitives");
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     try {
         // the light's record and matrix come back with the check's flag
@@ -1649,6 +1685,7 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
         std::vector<uint32_t> tab(firsts);
         tab.insert(tab.end(), pre.begin(), pre.end());
         tab.insert(tab.end(), mats.begin(), mats.end());
+        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
         HIP_TRY(hipSetDevice(s->device));
         bool finite = false;
         rc = update_xform(s->refit, records_of(s), tab, nr, rest_dev, (hipStream_t)stream,
@@ -1657,6 +1694,105 @@ int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32
     } catch (const std::exception &e) {
         return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
     }
+}
+
+// ---- the stream-ordered forms: the same host-side refusals with the same codes, then
+// update_async of rt_refit.hip -- enqueued on the caller's stream, no host wait.  The scene's host
+// flags (bounds_finite, nested) stay until the outcomes are folded (fold_updates).
+
+int rt_scene_update_triangles_async(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream,
+                                    uint64_t *ticket) {
+    const std::string who = "rt_scene_update_triangles_async";
+    const int k = async_arguments(s != nullptr, s ? s->num_prims : 0u, first, count, verts_dev, false);
+    if (k == kAsyncNullScene) return fail(RT_ERR_INVALID, who + ": null scene");
+    if (k == kAsyncEmpty) return RT_OK;
+    if (k == kAsyncNullRecords) return fail(RT_ERR_INVALID, who + ": null vertices");
+    int rc = refit_supported(s, who.c_str());
+    if (rc != RT_OK) return rc;
+    if (k == kAsyncRange) return fail(RT_ERR_INVALID, who + ": range outside the primitives");
+    if ((rc = require_triangles(s, first, count, who.c_str())) != RT_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return update_async(s->refit, records_of(s), TriVerts{first, verts_dev}, count, (hipStream_t)stream, 0, nullptr, 0, ticket);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, who + ": " + e.what());
+    }
+}
+
+int rt_scene_update_prims_async(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
+                                void *stream, uint64_t *ticket) {
+    const std::string who = "rt_scene_update_prims_async";
+    const int k = async_arguments(s != nullptr, s ? s->num_prims : 0u, first, count, prims_dev, true);
+    if (k == kAsyncNullScene) return fail(RT_ERR_INVALID, who + ": null scene");
+    if (k == kAsyncEmpty) return RT_OK;
+    if (k == kAsyncNullRecords) return fail(RT_ERR_INVALID, who + ": null records");
+    const int rc = refit_supported(s, who.c_str());
+    if (rc != RT_OK) return rc;
+    if (k == kAsyncRange) return fail(RT_ERR_INVALID, who + ": range outside the primitives");
+    // the light's SceneView fields are computed on the host from its record (fill_light), which this call never sees
+    if (k == kAsyncLight) return fail(RT_ERR_UNSUPPORTED, who + ": the range holds primitive 0 (the light moves through rt_scene_update_prims)");
+    HIP_TRY(hipSetDevice(s->device));
+    try {
+        return update_async(s->refit, records_of(s), PrimRecs{first, prims_dev, transforms_dev}, count, (hipStream_t)stream, 2, nullptr, 0,
+                            ticket);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, who + ": " + e.what());
+    }
+}
+
+int rt_scene_transform_triangles_async(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
+                                       void *stream, uint64_t *ticket) {
+    const char *who = "rt_scene_transform_triangles_async";
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null scene");
+    if (num_ranges == 0) return RT_OK;
+    if (!ranges) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null ranges");
+    int rc = refit_supported(s, who);
+    if (rc != RT_OK) return rc;
+    try {
+        // the table of rt_scene_transform_triangles: first[nr], prefix counts[nr + 1], matrices[16 nr]
+        std::vector<uint32_t> firsts, pre{0u}, mats;
+        std::vector<std::pair<uint32_t, uint32_t>> spans;
+        for (uint32_t r = 0; r < num_ranges; ++r) {
+            const rt_tri_xform &x = ranges[r];
+            if (x.count == 0) continue;
+            if ((uint64_t)x.first + x.count > s->num_prims)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: range " + std::to_string(r) + " outside the primitives");
+            if ((uint64_t)pre.back() + x.count > 0xffffffffull / 9u)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: too many triangles");
+            if ((rc = require_triangles(s, x.first, x.count, who)) != RT_OK) return rc;
+            firsts.push_back(x.first);
+            pre.push_back(pre.back() + x.count);
+            const uint32_t *m = reinterpret_cast<const uint32_t *>(x.M);
+            mats.insert(mats.end(), m, m + 16);
+            spans.push_back({x.first, x.count});
+        }
+        if (firsts.empty()) return RT_OK;
+        std::sort(spans.begin(), spans.end());
+        for (size_t k = 1; k < spans.size(); ++k)
+            if (spans[k - 1].first + spans[k - 1].second > spans[k].first)
+                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: ranges overlap");
+        if (!rest_dev) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null rest vertices");
+        const uint32_t nr = (uint32_t)firsts.size();
+        std::vector<uint32_t> tab(firsts);
+        tab.insert(tab.end(), pre.begin(), pre.end());
+        tab.insert(tab.end(), mats.begin(), mats.end());
+        HIP_TRY(hipSetDevice(s->device));
+        return update_xform_async(s->refit, records_of(s), tab, nr, rest_dev, (hipStream_t)stream, ticket);
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
+    }
+}
+
+int rt_scene_update_sync(rt_scene *s, rt_update_status *out) {
+    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_sync: null scene");
+    if (int rc = fold_updates(s); rc != RT_OK) return rc;
+    AsyncUpdates &U = s->refit.async;
+    if (out) *out = rt_update_status{U.submitted, U.applied, U.refused, U.first_refused};
+    // the earliest refusal since the previous sync is named and then forgotten
+    if (U.first_refused) (void)fail(RT_ERR_INVALID, U.first_refusal);
+    U.first_refused = 0;
+    U.first_refusal = nullptr;
+    return RT_OK;
 }
 
 // ---- the rebuild (rt_build.hip): built into fresh buffers, checked, and only then swapped in
@@ -1690,6 +1826,7 @@ int rt_scene_rebuild(rt_scene *s, void *stream) {
     if (rc != RT_OK) return rc;
     // the builder's decisions are min / max over keys of the floats: a NaN box (kept from creation) has no place in them
     if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: a primitive's box is NaN or infinite");
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     try {
         Rebuilt t;
@@ -1748,6 +1885,7 @@ int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, cons
     bool empty = false;
     int rc = splice_arguments(s, first, remove, prims_dev, insert, who, &empty);
     if (rc != RT_OK || empty) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     Rebuilt t;
     try {
@@ -1821,6 +1959,7 @@ int rt_scene_splice_ranges(rt_scene *s, const rt_tri_edit *edits, uint32_t num_e
         bool empty = false;
         int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty);
         if (rc != RT_OK || empty) return rc;
+        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
         HIP_TRY(hipSetDevice(s->device));
         RefitState &R = s->refit;
         std::vector<uint8_t> pinfo = splice_types(R.pinfo, plan);
@@ -1869,6 +2008,7 @@ int rt_scene_compact_triangles(rt_scene *s, const uint8_t *keep_dev, void *strea
     const char *who = "rt_scene_compact_triangles";
     int rc = compact_arguments(s, keep_dev, who);
     if (rc != RT_OK) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     Rebuilt t;
     try {
@@ -1925,6 +2065,7 @@ int rt_scene_splice_prims(rt_scene *s, const rt_prim_edit *edits, uint32_t num_e
         bool empty = false;
         int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty, true);
         if (rc != RT_OK || empty) return rc;
+        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
         HIP_TRY(hipSetDevice(s->device));
         RefitState &R = s->refit;
         SpliceKinds K;
@@ -1971,6 +2112,7 @@ int rt_scene_compact_prims(rt_scene *s, const uint8_t *keep_dev, void *stream) {
     const char *who = "rt_scene_compact_prims";
     int rc = compact_arguments(s, keep_dev, who);
     if (rc != RT_OK) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     Rebuilt t;
     try {
@@ -2020,6 +2162,7 @@ int rt_scene_set_prim_materials(rt_scene *s, uint32_t first, uint32_t count, con
     bool empty = false;
     int rc = materials_arguments(s, first, count, materials_dev, who, &empty);
     if (rc != RT_OK || empty) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     try {
         return set_materials(s->refit, records_of(s), first, count, materials_dev, s->num_materials, (hipStream_t)stream);
@@ -2052,6 +2195,7 @@ int rt_scene_prepare_updates(rt_scene *s, void *stream) {
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_prepare_updates: null scene");
     const int rc = refit_supported(s, who);
     if (rc != RT_OK) return rc;
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     HIP_TRY(hipSetDevice(s->device));
     try {
         return prepare_updates(s->refit, records_of(s), (hipStream_t)stream);
@@ -2062,6 +2206,7 @@ int rt_scene_prepare_updates(rt_scene *s, void *stream) {
 
 int rt_scene_update_plan_info(const rt_scene *s, uint32_t out[8]) {
     if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_update_plan_info: null argument");
+    if (int frc = fold_updates(const_cast<rt_scene *>(s)); frc != RT_OK) return frc;
     const RefitState &R = s->refit;
     const PlanInfo none{}, &p = R.refit_ready ? R.plan_info : none;
     out[0] = R.refit_ready ? 1u : 0u;
@@ -2077,6 +2222,7 @@ int rt_scene_update_plan_info(const rt_scene *s, uint32_t out[8]) {
 
 int rt_scene_copy_update_plan(const rt_scene *s, uint32_t *list, uint32_t *lvl, uint32_t *grp) {
     if (!s) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: null scene");
+    if (int frc = fold_updates(const_cast<rt_scene *>(s)); frc != RT_OK) return frc;
     const RefitState &R = s->refit;
     if (!R.refit_ready) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: no schedule is ready (rt_scene_prepare_updates)");
     HIP_TRY(hipSetDevice(s->device));
@@ -2092,6 +2238,7 @@ int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
     if (s->ext) kext::launch_intersect(s->view, rays, hits, n, stack_bytes(s), st);
     else kcore::launch_intersect(s->view, rays, hits, n, stack_bytes(s), st);
     HIP_TRY(hipGetLastError());
@@ -2103,6 +2250,7 @@ int rt_occluded(rt_scene *s, const rt_ray *rays, uint8_t *out, uint32_t n, void 
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
     if (s->ext) kext::launch_occluded(s->view, rays, out, n, stack_bytes(s), st);
     else kcore::launch_occluded(s->view, rays, out, n, stack_bytes(s), st);
     HIP_TRY(hipGetLastError());
@@ -2114,6 +2262,7 @@ int rt_intersect_packets(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
     if (s->ext) kext::launch_intersect_packet(s->view, rays, hits, n, st);
     else kcore::launch_intersect_packet(s->view, rays, hits, n, st);
     HIP_TRY(hipGetLastError());
@@ -2132,6 +2281,7 @@ int rt_trace(rt_scene *s, int mode, const rt_ray *rays, uint32_t *seeds, const u
     A.n = n; A.depth = depth;
     const bool tex = !s->view.sky_const;
     hipStream_t st = (hipStream_t)stream;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
     if (s->ext) kext::launch_trace(s->view, A, mode, max_depth_class(depth), tex, stack_bytes(s), st);
     else kcore::launch_trace(s->view, A, mode, max_depth_class(depth), tex, stack_bytes(s), st);
     HIP_TRY(hipGetLastError());
@@ -2201,6 +2351,7 @@ int rt_bvh_visualize(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t
     if (!s || (n && (!rays || !counts))) return fail(RT_ERR_INVALID, "rt_bvh_visualize: null argument");
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
+    if (int rc = after_updates(s, (hipStream_t)stream); rc != RT_OK) return rc;
     kcore::launch_visualize(s->view, rays, counts, n, stack_bytes(s), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -2212,6 +2363,7 @@ int rt_bvh_visualize_host(rt_scene *s, const rt_ray *rays, uint32_t *counts, uin
 // Tree cost of the scene's current device nodes (rt_cost.hip)
 int rt_scene_bvh_cost(rt_scene *s, rt_bvh_cost *out, void *stream) {
     if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_bvh_cost: null argument");
+    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
     if (!s->view.bounds_finite) return fail(RT_ERR_UNSUPPORTED, "rt_scene_bvh_cost: a node bound is NaN or infinite");
     HIP_TRY(hipSetDevice(s->device));
     rt_bvh_cost c{};

@@ -1,7 +1,8 @@
 // rt_refit.h -- in-place updates: the refit plan of a scene's tree (built in rt_scene_pack.cpp),
 // the update state a scene keeps, and the one host path of rt_refit.hip that every update entry
 // point of rt_device.hip takes (rt_scene_update_triangles, rt_scene_update_prims,
-// rt_scene_transform_triangles).  The per-lane text is in rt_update.h.
+// rt_scene_transform_triangles), with its stream-ordered form (update_async; the rt_scene_*_async
+// entry points and rt_scene_update_sync).  The per-lane text is in rt_update.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,6 +58,35 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 // rebuild puts slot map, slot boxes and centroids on the device, where they live from there on; the
 // schedule is built on the device (rt_plan.hip) by rt_scene_prepare_updates or else by the first
 // update, and again after a rebuild (rt_build.hip).
+// What a scene keeps for its stream-ordered updates, made by the first of them.
+//   status   the device block the kernels gate on and book into (UpdateStatus, rt_update.h);
+//   done     ONE event, recorded after every async update's settle step: whatever reads the scene
+//            afterwards waits on it (hipStreamWaitEvent) while `issued` is set, and so does the next
+//            async update, whose stream may be another -- the block has one writer at a time;
+//   ring     rt_scene_transform_triangles_async's range tables: kXformSlots pinned host slots, each
+//            with its device twin and the event of the update that read it.  A slot is taken again
+//            kXformSlots updates later; the call waits for its event only then.
+// The host's counts are folded from the block by drain_updates; kinds holds, per ticket since the
+// last fold, which entry point it came from (its refusal text).
+constexpr int kXformSlots = 8;
+struct XformSlot {
+    void *host = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+};
+struct AsyncUpdates {
+    void *status = nullptr;
+    hipEvent_t done = nullptr;
+    bool issued = false;            // an async update was enqueued since the last fold
+    uint64_t submitted = 0, applied = 0, refused = 0, first_refused = 0;
+    uint64_t folded = 0;            // tickets <= this are folded into the counts
+    const char *first_refusal = nullptr;
+    std::vector<uint8_t> kinds;     // ticket folded + 1 + k -> index into the refusal texts
+    XformSlot ring[kXformSlots];
+    uint32_t ring_next = 0;
+};
+
 struct RefitState {
     std::vector<uint8_t> pinfo;
     std::vector<float> pbox;
@@ -79,6 +109,7 @@ struct RefitState {
     size_t ranges_bytes = 0;
     void *d_types = nullptr;        // rt_scene_splice_prims' check: the inserted records' type bytes, kept between calls
     size_t types_bytes = 0;
+    AsyncUpdates async;             // stream-ordered updates (update_async)
 };
 void free_refit(RefitState &R);
 
@@ -127,7 +158,22 @@ int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hip
 // matrices[16 nr], uploaded to the scene's range table
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
                  hipStream_t st, const char *refusal, bool *finite);
-
+// The stream-ordered form of update(): everything is enqueued on `st` and the call returns.  Order:
+// wait for the scene's previous async update (any stream), the copies, the check (its flag stays on
+// the device), the gated write and refits, the settle step under `ticket` (= ++submitted), the
+// scene's event.  Blocks only to build a missing schedule (ensure_refit) and to create the status
+// block on a scene's first call.  `kind` indexes kRefusals.  *ticket_out may be null.
+extern const char *const kRefusals[3];
+template <class Src>
+int update_async(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, int kind,
+                 const UpdateCopy *copies, int ncopies, uint64_t *ticket_out);
+// ... for ranges of triangles: the table goes through the next slot of the ring (a bounded wait when
+// all kXformSlots are in flight)
+int update_xform_async(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
+                       hipStream_t st, uint64_t *ticket_out);
+// Waits for every enqueued async update and folds the block into the host's counts; *applied_new =
+// how many applied since the last fold.  Where none is pending it costs one branch.
+int drain_updates(RefitState &R, uint64_t *applied_new);
 
 // The schedule of the current topology (d_list, d_lvl, d_grp, plan.ntreelets, plan.has_top) built
 // on `st` from the device node array (rt_plan.hip); blocks.  The host tree is neither read nor

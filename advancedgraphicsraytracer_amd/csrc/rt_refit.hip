@@ -10,6 +10,11 @@
 //   k_refit_treelets   one workgroup per treelet (a whole subtree of at most kTreeletNodes nodes),
 //                      one height at a time (refit_level), a barrier between heights;
 //   k_refit_top        one workgroup, the same over the nodes above the cut.
+// The stream-ordered updates run k_check as it is and then
+//   k_write_if<Src>, k_refit_treelets_if, k_refit_top_if   the same text behind the gate: one
+//                      wave-uniform load of the check's flag (written by an EARLIER launch), and a
+//                      flagged update returns without a store;
+//   k_settle           one lane books the outcome into the scene's status block and clears the flag.
 // Src is one of the three sources of rt_update.h -- TriVerts (rt_scene_update_triangles), TriXform
 // (rt_scene_transform_triangles), PrimRecs (rt_scene_update_prims) -- and rt_update.h holds every
 // line a lane runs, so the CPU tests run the kernels' own text.
@@ -20,6 +25,8 @@
 #include "rt_refit.h"
 
 #include <cmath>
+#include <cstddef>
+#include <cstring>
 
 namespace rt {
 
@@ -46,6 +53,27 @@ __device__ __forceinline__ void refit_group(const RefitArgs &A, uint32_t g) {
 }
 __global__ void __launch_bounds__(256) k_refit_treelets(RefitArgs A) { refit_group(A, blockIdx.x); }
 __global__ void __launch_bounds__(1024) k_refit_top(RefitArgs A, uint32_t g) { refit_group(A, g); }
+
+// ---- behind the gate (update_gated, rt_update.h).  The flag's address is the same for every lane and
+// the launch that wrote it has ended, so every wave of a launch takes the same side: all of a
+// workgroup's waves reach refit_group's barriers or none does.
+template <class Src>
+__global__ void __launch_bounds__(256) k_write_if(RefitArgs A, Src src, uint32_t n, const UpdateStatus *status) {
+    if (update_gated(status)) return;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) src.write(A, i);
+}
+__global__ void __launch_bounds__(256) k_refit_treelets_if(RefitArgs A, const UpdateStatus *status) {
+    if (update_gated(status)) return;
+    refit_group(A, blockIdx.x);
+}
+__global__ void __launch_bounds__(1024) k_refit_top_if(RefitArgs A, uint32_t g, const UpdateStatus *status) {
+    if (update_gated(status)) return;
+    refit_group(A, g);
+}
+__global__ void __launch_bounds__(64) k_settle(UpdateStatus *status, uint64_t ticket) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) settle_update(status, ticket);
+}
 
 // the refit schedule of the current topology on the device: built there (rt_plan.hip) on the first
 // update of a scene and on the first after a rebuild, unless rt_scene_prepare_updates did so before
@@ -164,6 +192,15 @@ void free_refit(RefitState &R) {
     R.types_bytes = 0;
     R.refit_ready = false;
     R.plan_info = PlanInfo{};
+    AsyncUpdates &U = R.async;
+    if (U.status) (void)hipFree(U.status);
+    if (U.done) (void)hipEventDestroy(U.done);
+    for (XformSlot &x : U.ring) {
+        if (x.host) (void)hipHostFree(x.host);
+        if (x.dev) (void)hipFree(x.dev);
+        if (x.ev) (void)hipEventDestroy(x.ev);
+    }
+    U = AsyncUpdates{};
 }
 
 template <class Src>
@@ -202,6 +239,132 @@ template int update<TriVerts>(RefitState &, const SceneRecords &, const TriVerts
                               const UpdateCopy *, int, bool *);
 template int update<PrimRecs>(RefitState &, const SceneRecords &, const PrimRecs &, uint32_t, hipStream_t, const char *,
                               const UpdateCopy *, int, bool *);
+
+// ---- the stream-ordered path
+
+const char *const kRefusals[3] = {
+    "rt_scene_update_triangles_async: a vertex is NaN or infinite",
+    "rt_scene_transform_triangles_async: a transformed vertex is NaN or infinite",
+    "rt_scene_update_prims_async: a record's type or material is not the scene's, or a field, transform or box is NaN or infinite",
+};
+
+int drain_updates(RefitState &R, uint64_t *applied_new) {
+    AsyncUpdates &U = R.async;
+    if (applied_new) *applied_new = 0;
+    if (!U.issued) return RT_OK;
+    HIP_TRY(hipEventSynchronize(U.done));   // every async update waited for the one before it
+    UpdateStatus h{};
+    HIP_TRY(hipMemcpy(&h, U.status, sizeof(h), hipMemcpyDeviceToHost));
+    if (h.first_refused) {
+        if (!U.first_refused) {
+            U.first_refused = h.first_refused;
+            U.first_refusal = kRefusals[U.kinds[(size_t)(h.first_refused - U.folded - 1u)]];
+        }
+        HIP_TRY(hipMemset((char *)U.status + offsetof(UpdateStatus, first_refused), 0, sizeof(uint64_t)));
+    }
+    if (applied_new) *applied_new = h.applied - U.applied;
+    U.applied = h.applied;
+    U.refused = h.refused;
+    U.folded = U.submitted;
+    U.kinds.clear();
+    U.issued = false;
+    return RT_OK;
+}
+
+// the status block and the event, once per scene (blocks: the block is cleared with a plain memset)
+static int ensure_async(AsyncUpdates &U) {
+    if (U.status) return RT_OK;
+    if (!U.done) HIP_TRY(hipEventCreateWithFlags(&U.done, hipEventDisableTiming));
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(UpdateStatus)));
+    if (hipMemset(p, 0, sizeof(UpdateStatus)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(p);
+        return fail(RT_ERR_HIP, "hipMemset failed");
+    }
+    U.status = p;
+    return RT_OK;
+}
+
+template <class Src>
+int update_async(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, int kind,
+                 const UpdateCopy *copies, int ncopies, uint64_t *ticket_out) {
+    AsyncUpdates &U = R.async;
+    int rc = RT_OK;
+    if (!R.refit_ready || !U.status) {
+        // no schedule (the scene's first update, or the first after a rebuild), or no status block
+        // yet: built here, behind everything that still reads the scene -- the one blocking case
+        if ((rc = drain_updates(R, nullptr)) != RT_OK) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        if ((rc = ensure_refit(R, S, st)) != RT_OK || (rc = ensure_async(U)) != RT_OK) return rc;
+    }
+    const RefitArgs A = refit_args(R, S);
+    UpdateStatus *status = (UpdateStatus *)U.status;
+    const dim3 grid((n + 255u) / 256u), block(256);
+    // behind the previous async update, whatever stream it ran on: the block has one writer
+    if (U.issued) HIP_TRY(hipStreamWaitEvent(st, U.done, 0));
+    for (const UpdateCopy *c = copies; c < copies + ncopies; ++c) HIP_TRY(hipMemcpyAsync(c->dst, c->src, c->bytes, c->kind, st));
+    const uint64_t ticket = U.submitted + 1u;
+    // the check is a pass of its own; its flag stays on the device, where the launches below read it
+    hipLaunchKernelGGL(k_check<Src>, grid, block, 0, st, A, src, n, &status->flag);
+    hipLaunchKernelGGL(k_write_if<Src>, grid, block, 0, st, A, src, n, (const UpdateStatus *)status);
+    hipLaunchKernelGGL(k_refit_treelets_if, dim3(R.plan.ntreelets), dim3(256), 0, st, A, (const UpdateStatus *)status);
+    if (R.plan.has_top)
+        hipLaunchKernelGGL(k_refit_top_if, dim3(1), dim3(1024), 0, st, A, R.plan.ntreelets, (const UpdateStatus *)status);
+    hipLaunchKernelGGL(k_settle, dim3(1), dim3(64), 0, st, status, ticket);
+    const hipError_t launched = hipGetLastError();
+    // whatever was enqueued, the scene's readers and the next update wait for it
+    const hipError_t recorded = hipEventRecord(U.done, st);
+    U.issued = true;
+    R.bvh_stale = true;
+    U.submitted = ticket;
+    U.kinds.push_back((uint8_t)kind);
+    HIP_TRY(launched);
+    HIP_TRY(recorded);
+    if (ticket_out) *ticket_out = ticket;
+    return RT_OK;
+}
+template int update_async<TriVerts>(RefitState &, const SceneRecords &, const TriVerts &, uint32_t, hipStream_t, int,
+                                    const UpdateCopy *, int, uint64_t *);
+template int update_async<PrimRecs>(RefitState &, const SceneRecords &, const PrimRecs &, uint32_t, hipStream_t, int,
+                                    const UpdateCopy *, int, uint64_t *);
+
+int update_xform_async(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
+                       hipStream_t st, uint64_t *ticket_out) {
+    AsyncUpdates &U = R.async;
+    XformSlot &x = U.ring[U.ring_next];
+    const size_t need = sizeof(uint32_t) * tab.size();
+    // the slot's last update, kXformSlots calls ago, has read it: the one wait of this call, and it
+    // returns at once unless all the slots are in flight
+    if (x.used) HIP_TRY(hipEventSynchronize(x.ev));
+    if (!x.ev) HIP_TRY(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
+    if (need > x.bytes) {
+        const size_t cap = std::max<size_t>(4096, 2 * need);
+        if (x.host) HIP_TRY(hipHostFree(x.host));
+        x.host = nullptr;
+        if (x.dev) HIP_TRY(hipFree(x.dev));
+        x.dev = nullptr;
+        x.bytes = 0;
+        HIP_TRY(hipHostMalloc(&x.host, cap, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(&x.dev, cap));
+        x.bytes = cap;
+    }
+    std::memcpy(x.host, tab.data(), need);
+    TriXform src{};
+    src.R.first = (const uint32_t *)x.dev;
+    src.R.pre = src.R.first + nr;
+    src.R.M = (const float *)(src.R.pre + nr + 1);
+    src.R.nr = nr;
+    src.rest = rest_dev;
+    const UpdateCopy table{x.dev, x.host, need, hipMemcpyHostToDevice};
+    const uint64_t before = U.submitted;
+    const int rc = update_async(R, S, src, tab[2 * (size_t)nr], st, 1, &table, 1, ticket_out);
+    if (U.submitted != before) {   // enqueued (even where a later step failed): the slot is taken
+        x.used = true;
+        U.ring_next = (U.ring_next + 1u) % (uint32_t)kXformSlots;
+        HIP_TRY(hipEventRecord(x.ev, st));
+    }
+    return rc;
+}
 
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
                  hipStream_t st, const char *refusal, bool *finite) {

@@ -201,4 +201,38 @@ RT_HD void refit_level(const RefitArgs &A, uint32_t l, uint32_t tid, uint32_t st
     for (uint32_t i = A.lvl[l] + tid; i < e; i += stride) refit_node(A, A.list[i]);
 }
 
+// ---- stream-ordered updates: nobody on the host reads the check's flag.  It lives in
+// the scene's status block; the write and the refit launches of the same update read it (the gate)
+// and return without a store when it is set, and one lane then books the outcome and clears it for
+// the next update (the settle step).  One stream order, one writer: plain loads and stores, the
+// flag always written by an earlier launch than the one that reads it.
+struct UpdateStatus {
+    uint32_t flag, pad;       // the check of the update in flight refused it (k_check sets, settle_update clears)
+    uint64_t applied, refused;   // updates since the scene was created
+    uint64_t first_refused;   // ticket of the earliest refusal since the host last read the block (0: none)
+};
+// What the stream-ordered entry points refuse without the device or the records' contents, in the
+// blocking calls' order (the scene-kind refusals -- SBVH, RT_PT_QUADS -- come between kAsyncNullRecords
+// and kAsyncRange).  light_stays: rt_scene_update_prims_async, where primitive 0 moves through the
+// blocking call alone.
+enum { kAsyncOk = 0, kAsyncNullScene, kAsyncEmpty, kAsyncNullRecords, kAsyncRange, kAsyncLight };
+RT_HD int async_arguments(bool scene, uint32_t num_prims, uint32_t first, uint32_t count, const void *recs, bool light_stays) {
+    if (!scene) return kAsyncNullScene;
+    if (count == 0) return kAsyncEmpty;
+    if (!recs) return kAsyncNullRecords;
+    if ((uint64_t)first + count > num_prims) return kAsyncRange;
+    if (light_stays && first == 0) return kAsyncLight;
+    return kAsyncOk;
+}
+RT_HD bool update_gated(const UpdateStatus *st) { return st->flag != 0u; }
+RT_HD void settle_update(UpdateStatus *st, uint64_t ticket) {
+    if (st->flag != 0u) {
+        st->refused += 1u;
+        if (st->first_refused == 0u) st->first_refused = ticket;
+    } else {
+        st->applied += 1u;
+    }
+    st->flag = 0u;
+}
+
 }  // namespace rt

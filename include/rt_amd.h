@@ -291,6 +291,62 @@ int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, cons
 typedef struct { uint32_t first, count; float M[16]; } rt_tri_xform;
 int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
                                  void *stream);
+/* Stream-ordered forms of the three in-place updates: the same records written, the same refit, the
+ * same "untouched on refusal" contract, but no host wait.  The call enqueues on `stream` and returns;
+ * a host that animates every frame runs ahead of the GPU across updates and frames as it does across
+ * frames.  *ticket (may be NULL) receives the update's number, 1, 2, ... per scene.
+ * Refused at once, with the blocking call's code and without consuming a ticket: everything the
+ * blocking call checks on the host (null pointers, ranges, non-triangles, overlapping ranges, SBVH or
+ * RT_PT_QUADS=1 scenes); count == 0 / no range is RT_OK.  rt_scene_update_prims_async over a range
+ * that holds primitive 0 is RT_ERR_UNSUPPORTED: the light's fields are computed on the host from its
+ * record, so the light moves through the blocking call.
+ * Refused on the device: the finiteness / admissibility check still runs as a pass of its own before
+ * anything is written, but its flag is read by the kernels that follow, not by the host -- a flagged
+ * update's write and refit launches store nothing (node bytes of a caller's loose prebuilt tree stay
+ * as they were), and the outcome shows at rt_scene_update_sync.  Later updates in the queue do not
+ * depend on an earlier refusal.
+ * Ordering the library provides:
+ *   1. the update runs after everything enqueued on `stream` before it, frames of any renderer
+ *      submitted on that stream included (their kernels on renderer streams are joined into the
+ *      submitting stream by the frame's finishing pass);
+ *   2. everything enqueued after it that reads the scene waits for it, on whatever stream: frames
+ *      (on renderer streams and on caller streams), shards and multi-GPU frames, rt_intersect*,
+ *      rt_occluded, rt_trace, rt_bvh_visualize, rt_renderer_tile_work, and a later async update on
+ *      another stream.  A scene that never had an async update pays one host branch per launch;
+ *   3. work enqueued EARLIER on other streams of the caller's is the caller's to order (plain HIP
+ *      semantics): a frame submitted on stream B and not yet finished may see an update enqueued
+ *      afterwards on stream A;
+ *   4. every blocking scene entry point (the blocking updates and their _host forms,
+ *      rt_scene_prepare_updates, rt_scene_rebuild, the splices and compactions,
+ *      rt_scene_set_prim_materials, rt_scene_copy_bvh, rt_scene_bvh_cost, rt_scene_update_plan_info,
+ *      rt_scene_copy_update_plan, rt_scene_destroy) first does what rt_scene_update_sync does, so
+ *      the two styles mix safely.
+ * Pointer lifetime: verts_dev, rest_dev, prims_dev and transforms_dev must stay valid and unchanged
+ * until the update has executed in stream order; the host `ranges` array is consumed before the
+ * call returns (it travels through a scene-owned ring of 8 pinned slots: the call waits for the
+ * update that used its slot 8 calls ago, i.e. only while all 8 are in flight, and a table larger
+ * than any before it reallocates its slot).
+ * Host waits that remain: where no refit schedule is ready (the first update of a scene, the first
+ * after a rebuild or a splice) the call builds it inside itself and blocks that once, like the
+ * blocking update -- rt_scene_prepare_updates beforehand keeps it non-blocking -- and a scene's
+ * first async call creates its status block.
+ * The next frame is rendered with reset = 1.  The host-side flags behind the fast paths
+ * (bounds_finite, the wave walk's nesting) stay as they are until rt_scene_update_sync; frames are
+ * identical either way. */
+int rt_scene_update_triangles_async(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev,
+                                    void *stream, uint64_t *ticket);
+int rt_scene_transform_triangles_async(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges,
+                                       const float *rest_dev, void *stream, uint64_t *ticket);
+int rt_scene_update_prims_async(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev,
+                                const float *transforms_dev, void *stream, uint64_t *ticket);
+/* submitted: tickets handed out; applied, refused: updates that ran since the scene was created;
+ * first_refused: ticket of the earliest refusal since the previous rt_scene_update_sync, 0 for none */
+typedef struct { uint64_t submitted, applied, refused, first_refused; } rt_update_status;
+/* Waits for every enqueued async update (not for frames), folds their outcomes into the scene's host
+ * state and fills *out (may be NULL).  RT_OK also where an update was refused: first_refused says
+ * so, and rt_last_error() then names that refusal.
+ *   RT_ERR_INVALID      null scene. */
+int rt_scene_update_sync(rt_scene *s, rt_update_status *out);
 /* Rebuild the scene's plain BVH on the GPU from its CURRENT primitives (after any number of
  * in-place updates): afterwards the scene is bit for bit a fresh rt_scene_create of the current
  * description -- node array, primitive-index array, leaf-slot records in the new slot order,

@@ -289,6 +289,32 @@ class Scene {   // template/scene.h:37
     void TransformTriangles(const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev, void *stream = nullptr) {
         rt_check(rt_scene_transform_triangles(handle(), ranges, num_ranges, rest_dev, stream));
     }
+    // The stream-ordered forms of the three device updates (rt_scene_*_async): enqueued on the hipStream_t
+    // and returned from at once, so a host that animates every frame runs ahead of the GPU; everything
+    // submitted afterwards that reads the scene waits for them on the device.  The pointers stay valid
+    // until the update has run; the light (primitive 0) moves through UpdatePrimitivesDevice.  Each returns
+    // its ticket (0: nothing to do); UpdateSync waits for them all and says what became of them.
+    uint64_t UpdateTrianglesAsync(uint32_t first, const float *verts_dev, uint32_t count, void *stream = nullptr) {
+        uint64_t ticket = 0;
+        rt_check(rt_scene_update_triangles_async(handle(), first, count, verts_dev, stream, &ticket));
+        return ticket;
+    }
+    uint64_t UpdatePrimitivesAsync(uint32_t first, const rt_prim *prims_dev, const float *transforms_dev, uint32_t count,
+                                   void *stream = nullptr) {
+        uint64_t ticket = 0;
+        rt_check(rt_scene_update_prims_async(handle(), first, count, prims_dev, transforms_dev, stream, &ticket));
+        return ticket;
+    }
+    uint64_t TransformTrianglesAsync(const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev, void *stream = nullptr) {
+        uint64_t ticket = 0;
+        rt_check(rt_scene_transform_triangles_async(handle(), ranges, num_ranges, rest_dev, stream, &ticket));
+        return ticket;
+    }
+    rt_update_status UpdateSync() {
+        rt_update_status st{};
+        rt_check(rt_scene_update_sync(handle(), &st));
+        return st;
+    }
     // Scene::BuildBVH (template/scene.h:845): the tree of the current primitives, rebuilt on the GPU after
     // in-place updates have moved them; the next Tick resets the accumulator
     void BuildBVH(void *stream = nullptr) { rt_check(rt_scene_rebuild(handle(), stream)); }
