@@ -1,4 +1,5 @@
-// rt_device.hip -- the device half of the C-ABI: scene upload, renderer state, launches.
+// rt_device.hip -- the device half of the C-ABI: scene upload, renderer state, launches (the entry points
+// that change a live scene are rt_scene_edit.hip; struct rt_scene is rt_scene.h).
 // The kernels live in rt_kernels.inc (built twice: rt_kern_core.hip / rt_kern_ext.hip).
 //
 // Hot path: Renderer::Tick -> Camera::GetPrimaryRay -> Renderer::Trace
@@ -36,79 +37,11 @@
 #include "rt_internal.h"
 #include "rt_records.h"
 #include "rt_refit.h"
-#include "rt_splice.h"
+#include "rt_scene.h"
 #include "rt_tune.h"
 
 // ====================================================================== host side
 using namespace rt;
-
-struct rt_scene {
-    int device = 0;
-    SceneView view{};
-    Bvh bvh;
-    uint32_t num_prims = 0;
-    uint32_t num_materials = 0; // what an inserted triangle's material index is checked against
-    uint32_t stack_depth = 0;   // LDS stack entries per lane
-    int frame_waves = 0;        // primary+shadow frame kernel build (frame_build): 0 = chosen, 7 = the
-                                // plain build, 8 = the single-sample one wherever it applies (RT_FRAME_WAVES)
-    uint32_t num_cus = 256;     // CUs of the device (resident grids, frames-in-flight rules)
-    bool has_cubes = false;     // cube acceptance depends on the visiting order: no wave walk
-    bool quads = false;         // two-level node records built (RT_PT_QUADS=1, build_quads)
-    bool quad_lanes = false;    // ... and the lane kernel walks them
-    void *d_quads = nullptr;
-    bool walk_fits = true;      // the lane stacks + the wave walk's word stack fit one launch's LDS (kLdsLaunchMax)
-    bool nested = true;         // every child box lies inside its parent's (as floats): the wave walk's
-                                // exactness needs it (the builders' trees always; a caller's prebuilt one
-                                // is checked at rt_scene_create)
-    int walk = RT_WALK_LANE;    // camera-ray walk of the global-node primary+shadow kernel
-    bool ext = false;           // needs the kext kernels (cubes, quads, textures, non-Light light)
-    bool ext_fixed = false;     // ... for reasons no edit of the primitives changes (family_fixed): kept for
-                                // the commit of rt_scene_splice_prims, which takes ext anew by creation's rule
-    bool pt_lanes = true;           // levels >= 1 run the lane state machine (RT_PT_LANES=0: k_pt_level)
-    bool pt_dynamic = true;         // wavefront levels >= 1 fetch chunks dynamically (RT_PT_DYNAMIC=0: static)
-    bool pt_wavefront = true;   // depth >= 2 path tracing: wavefront (k_pt_level) vs one kernel (k_render)
-    uint32_t pt_drain_level = 64;   // bounce level from which the wavefront always drains (64 = never forced)
-    double pt_drain_rounds = 0.25;  // ... and it drains any level holding <= this many rounds of resident lanes
-    // small batches (<= pt_small_rounds rounds of resident lanes, e.g. a 1/8 shard's): always drain
-    // from level pt_drain_small (0 = off).  Config 5's 1/8 shard (4.1 M paths per batch, ~10 rounds):
-    // 1.126 / 1.129 -> 1.055 / 1.059 ms forced from level 4 (1.095 / 1.068 from 3); whole frames
-    // (33 M paths, ~84 rounds) lose with it (CFG5-sub 6.70 -> 6.85 ms), so they keep the threshold
-    // alone (profiles/r05/c5drain)
-    uint32_t pt_drain_small = 4;
-    double pt_small_rounds = 16.0;
-    // ... and drains any of its levels holding <= this many rounds (the whole frames' 0.25 above):
-    // the 1/8 shard 1.084 / 1.077 -> 1.054 / 1.065 ms mean of three interleaved runs (0.0625: 1.058;
-    // 0.5: 1.092; profiles/r05/c5drain/c5knobs*.jsonl)
-    double pt_small_drain_rounds = 0.125;
-    bool tile_order = true;         // measured-cost (longest first) tile order (RT_TILE_ORDER=0: off)
-    uint32_t split_units = 40000;   // sample split below this many tiles (1080p = 32,400 tiles)
-    bool xcd_order = false;         // measured order grouped by XCD: blocks b, b + 8, ... (one XCD) render
-                                    // one compact screen region of 1/8 of the frame's cost (L2 locality)
-    uint32_t split_parts = 2;       // ... each as this many waves of 64 / parts lanes (RT_SPLIT_PARTS: 2, 4, 8)
-    int32_t heavy_split = -1;       // primary+shadow frames: the costliest tiles run as two half-tile
-                                    // waves (RT_SPLIT_HEAVY = count; -1: ntiles / 32)
-    uint64_t pt_mem_bytes = 12288ull << 20;   // path-state budget per slot (two when pipelined): 12 GB
-                                              // of the 288 GB HBM holds all 16 spp of a 1080p depth-10 frame
-    bool pt_pipeline = true;        // sample batches alternate path-state slots and streams
-    uint32_t pt_slots = 0;          // path-state slots / streams of pipelined frames (RT_PT_SLOTS, 2-8;
-                                    // 0 = 8 for batches of <= 8.4 M paths, else 4)
-                                    // (RT_PT_PIPELINE=0: one slot, the caller's stream)
-    uint32_t ps_buffers = 0;        // per-sample result buffers of overlapped frames (RT_PS_BUFFERS,
-                                    // 2-7; 0 = frames in flight + 1)
-    int32_t ps_pipeline = -1;       // primary+shadow frames overlap: -1 timed per renderer (auto),
-                                    // 0 never, 1 always (RT_PS_PIPELINE)
-    uint32_t ps_depth = 2;          // frames in flight when forced (RT_PS_DEPTH, 2-8)
-    float tune_delay_ms = 100.0f;   // GPU time a parameter set runs before its timed choices start
-                                    // (RT_TUNE_DELAY_MS): the clocks ramp over ~0.1 s, and choices
-                                    // timed on the first frames at low clocks came out wrong
-    void *d_nodes = nullptr, *d_prims = nullptr, *d_shade = nullptr, *d_mats = nullptr, *d_sky = nullptr;
-    void *d_xprims = nullptr, *d_tex = nullptr;
-    void *d_scratch = nullptr;  // staging for the host-pointer batched calls
-    void *d_cost = nullptr;     // rt_scene_bvh_cost's partial sums (rt_cost.hip), allocated by its first call
-    size_t scratch_bytes = 0;
-    hipStream_t stream = nullptr;
-    RefitState refit;           // in-place updates (rt_refit.h)
-};
 
 // renderer streams: up to 8 -- frames in flight of overlapped primary+shadow frames (timed
 // choice among 2 / 4 / 6, forced up to 8) and the path-state slots of pipelined path-traced
@@ -233,14 +166,6 @@ namespace {
 
 enum { kWalk, kSplit, kOverlap, kGate };   // rt_renderer::tune_ev rows
 
-// A stream that is about to read the scene waits for its stream-ordered updates: the
-// scene's one event, and only while an async update is pending -- otherwise one branch.
-inline int after_updates(const rt_scene *s, hipStream_t st) {
-    if (!s->refit.async.issued) return RT_OK;
-    HIP_TRY(hipStreamWaitEvent(st, s->refit.async.done, 0));
-    return RT_OK;
-}
-
 void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -290,11 +215,13 @@ int pack_options_from_env(PackOptions &o) {
     return RT_OK;
 }
 
+}  // namespace
+
 // Every scene field that follows from the tree, set here for a created scene and for a rebuilt one
 // (s->bvh's nodes_used, depth and max_leaf and the device node / slot arrays are already the tree's).
 // The camera-walk policy is not the tree's: creation derives it afterwards (scene_knobs_from_env), a
 // rebuild keeps it unless the new tree no longer admits the wave walk.
-void scene_tree_fields(rt_scene *s, uint32_t root_word, bool nested, bool bounds_finite) {
+void rt::scene_tree_fields(rt_scene *s, uint32_t root_word, bool nested, bool bounds_finite) {
     s->stack_depth = pick_stack(s->bvh.depth);
     s->walk_fits = stack_admits_walk(s->stack_depth);
     s->nested = nested;
@@ -311,6 +238,8 @@ void scene_tree_fields(rt_scene *s, uint32_t root_word, bool nested, bool bounds
     if (const char *e = std::getenv("RT_XCD_ORDER")) s->xcd_order = std::atoi(e) != 0;
     if (s->walk != RT_WALK_LANE && !(s->nested && s->walk_fits)) s->walk = RT_WALK_LANE;
 }
+
+namespace {
 
 // the scene's launch policy: defaults from the tree, overridden by the environment (A/B runs)
 void scene_knobs_from_env(rt_scene *s) {
@@ -1474,23 +1403,6 @@ int rt_scene_create_recipe_ex(const char *name, const char *mesh_dir, int32_t de
     }
 }
 
-// What rt_scene_update_sync does, and every blocking scene entry point first: waits for the enqueued
-// async updates and folds their outcomes into the host's state.  The root of a checked refit over
-// finite primitive boxes is finite by construction, so the flags rise as after a blocking update,
-// without a read-back.  A scene without pending async updates pays one branch.
-static int fold_updates(rt_scene *s) {
-    if (!s->refit.async.issued) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    uint64_t applied = 0;
-    const int rc = drain_updates(s->refit, &applied);
-    if (rc != RT_OK) return rc;
-    if (applied) {
-        s->view.bounds_finite = s->refit.boxes_finite ? 1 : 0;
-        if (s->refit.boxes_finite) s->nested = true;
-    }
-    return RT_OK;
-}
-
 int rt_scene_destroy(rt_scene *s) {
     free_scene(s);   // waits for the whole device: nothing of an async update is left to fold
     return RT_OK;
@@ -1536,700 +1448,6 @@ int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
     }
     std::memcpy(nodes, s->bvh.nodes.data(), sizeof(Node) * s->bvh.nodes_used);
     std::memcpy(indices, s->bvh.indices.data(), sizeof(uint32_t) * s->bvh.indices.size());
-    return RT_OK;
-}
-
-// ---- in-place updates.  The entry points check their arguments; the device work -- check, write,
-// refit, one path for all of them -- is update() of rt_refit.hip.
-
-// an in-place update needs a plain tree (every primitive in one leaf) with the binary node array alone
-static int refit_supported(const rt_scene *s, const char *who) {
-    if (s->bvh.indices.size() != s->num_prims)
-        return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": an SBVH scene (leaves share primitives) cannot be refitted");
-    if (s->quads) return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": scene built with two-level node records (RT_PT_QUADS=1)");
-    return RT_OK;
-}
-static int require_triangles(const rt_scene *s, uint32_t first, uint32_t count, const char *who) {
-    for (uint32_t id = first; id < first + count; ++id)
-        if ((s->refit.pinfo[id] & 0x7f) != RT_TRIANGLE)
-            return fail(RT_ERR_INVALID, std::string(who) + ": primitive " + std::to_string(id) + " is not a triangle");
-    return RT_OK;
-}
-static SceneRecords records_of(rt_scene *s) {
-    return SceneRecords{&s->bvh, s->num_prims, s->d_nodes, s->d_prims, s->d_shade, s->d_xprims, s->view.walk_margin};
-}
-// after an update: the scene's flags from the new root box
-static int settle(rt_scene *s, int rc, bool finite) {
-    if (rc != RT_OK) return rc;
-    s->view.bounds_finite = finite ? 1 : 0;
-    if (finite) s->nested = true;   // every box is now the union of finite boxes below it
-    return RT_OK;
-}
-
-int rt_scene_update_triangles(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream) {
-    const char *who = "rt_scene_update_triangles";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null scene");
-    if (count == 0) return RT_OK;
-    if (!verts_dev) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: null vertices");
-    int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles: range outside the primitives");
-    if ((rc = require_triangles(s, first, count, who)) != RT_OK) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        bool finite = false;
-        rc = update(s->refit, records_of(s), TriVerts{first, verts_dev}, count, (hipStream_t)stream,
-                    "rt_scene_update_triangles: a vertex is NaN or infinite", nullptr, 0, &finite);
-        return settle(s, rc, finite);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_update_triangles_host(rt_scene *s, uint32_t first, uint32_t count, const float *verts) {
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: null scene");
-    if (count == 0) return RT_OK;
-    if (!verts) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: null vertices");
-    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_triangles_host: range outside the primitives");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-    const size_t need = 36 * (size_t)count;
-    int rc = grow(&s->d_scratch, &s->scratch_bytes, need);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_scratch, verts, need, hipMemcpyHostToDevice, s->stream));
-    return rt_scene_update_triangles(s, first, count, (const float *)s->d_scratch, s->stream);
-}
-
-int rt_scene_update_prims(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
-                          void *stream) {
-    const char *who = "rt_scene_update_prims";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null scene");
-    if (count == 0) return RT_OK;
-    if (!prims_dev) return fail(RT_ERR_INVALID, "rt_scene_update_prims: null records");
-    int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims: range outside the primitives");
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        // the light's record and matrix come back with the check's flag
-        rt_prim light{};
-        float lightT[16];
-        bool finite = false;
-        const UpdateCopy back[2] = {{&light, prims_dev, sizeof(light), hipMemcpyDeviceToHost},
-                                    {lightT, transforms_dev, sizeof(lightT), hipMemcpyDeviceToHost}};
-        rc = update(s->refit, records_of(s), PrimRecs{first, prims_dev, transforms_dev}, count, (hipStream_t)stream,
-                    "rt_scene_update_prims: a record's type or material is not the scene's, or a field, "
-                    "transform or box is NaN or infinite",
-                    back, first != 0 ? 0 : transforms_dev ? 2 : 1, &finite);
-        // SceneView travels by value with every launch (renderers and the multi-GPU frames read
-        // s->view per frame), so the light's fields change here and nowhere else
-        if (rc == RT_OK && first == 0) fill_light(light, transforms_dev ? lightT : nullptr, s->view);
-        return settle(s, rc, finite);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_update_prims_host(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims, const float *transforms) {
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: null scene");
-    if (count == 0) return RT_OK;
-    if (!prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: null records");
-    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, "rt_scene_update_prims_host: range outside the primitives");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-    const size_t pbytes = (sizeof(rt_prim) * (size_t)count + 15u) & ~(size_t)15u, tbytes = transforms ? 64 * (size_t)count : 0;
-    int rc = grow(&s->d_scratch, &s->scratch_bytes, pbytes + tbytes);
-    if (rc != RT_OK) return rc;
-    char *base = (char *)s->d_scratch;
-    HIP_TRY(hipMemcpyAsync(base, prims, sizeof(rt_prim) * (size_t)count, hipMemcpyHostToDevice, s->stream));
-    if (transforms) HIP_TRY(hipMemcpyAsync(base + pbytes, transforms, tbytes, hipMemcpyHostToDevice, s->stream));
-    return rt_scene_update_prims(s, first, count, (const rt_prim *)base, transforms ? (const float *)(base + pbytes) : nullptr,
-                                 s->stream);
-}
-
-int rt_scene_transform_triangles(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
-                                 void *stream) {
-    const char *who = "rt_scene_transform_triangles";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null scene");
-    if (num_ranges == 0) return RT_OK;
-    if (!ranges) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null ranges");
-    int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    try {
-        // the table: first[nr], prefix counts[nr + 1], matrices[16 nr] -- empty ranges dropped
-        std::vector<uint32_t> firsts, pre{0u}, mats;
-        std::vector<std::pair<uint32_t, uint32_t>> spans;
-        for (uint32_t r = 0; r < num_ranges; ++r) {
-            const rt_tri_xform &x = ranges[r];
-            if (x.count == 0) continue;
-            if ((uint64_t)x.first + x.count > s->num_prims)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: range " + std::to_string(r) + " outside the primitives");
-            if ((uint64_t)pre.back() + x.count > 0xffffffffull / 9u)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: too many triangles");
-            if ((rc = require_triangles(s, x.first, x.count, who)) != RT_OK) return rc;
-            firsts.push_back(x.first);
-            pre.push_back(pre.back() + x.count);
-            const uint32_t *m = reinterpret_cast<const uint32_t *>(x.M);
-            mats.insert(mats.end(), m, m + 16);
-            spans.push_back({x.first, x.count});
-        }
-        if (firsts.empty()) return RT_OK;
-        std::sort(spans.begin(), spans.end());
-        for (size_t k = 1; k < spans.size(); ++k)
-            if (spans[k - 1].first + spans[k - 1].second > spans[k].first)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: ranges overlap");
-        if (!rest_dev) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles: null rest vertices");
-        const uint32_t nr = (uint32_t)firsts.size();
-        std::vector<uint32_t> tab(firsts);
-        tab.insert(tab.end(), pre.begin(), pre.end());
-        tab.insert(tab.end(), mats.begin(), mats.end());
-        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-        HIP_TRY(hipSetDevice(s->device));
-        bool finite = false;
-        rc = update_xform(s->refit, records_of(s), tab, nr, rest_dev, (hipStream_t)stream,
-                          "rt_scene_transform_triangles: a transformed vertex is NaN or infinite", &finite);
-        return settle(s, rc, finite);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-// ---- the stream-ordered forms: the same host-side refusals with the same codes, then
-// update_async of rt_refit.hip -- enqueued on the caller's stream, no host wait.  The scene's host
-// flags (bounds_finite, nested) stay until the outcomes are folded (fold_updates).
-
-int rt_scene_update_triangles_async(rt_scene *s, uint32_t first, uint32_t count, const float *verts_dev, void *stream,
-                                    uint64_t *ticket) {
-    const std::string who = "rt_scene_update_triangles_async";
-    const int k = async_arguments(s != nullptr, s ? s->num_prims : 0u, first, count, verts_dev, false);
-    if (k == kAsyncNullScene) return fail(RT_ERR_INVALID, who + ": null scene");
-    if (k == kAsyncEmpty) return RT_OK;
-    if (k == kAsyncNullRecords) return fail(RT_ERR_INVALID, who + ": null vertices");
-    int rc = refit_supported(s, who.c_str());
-    if (rc != RT_OK) return rc;
-    if (k == kAsyncRange) return fail(RT_ERR_INVALID, who + ": range outside the primitives");
-    if ((rc = require_triangles(s, first, count, who.c_str())) != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        return update_async(s->refit, records_of(s), TriVerts{first, verts_dev}, count, (hipStream_t)stream, 0, nullptr, 0, ticket);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, who + ": " + e.what());
-    }
-}
-
-int rt_scene_update_prims_async(rt_scene *s, uint32_t first, uint32_t count, const rt_prim *prims_dev, const float *transforms_dev,
-                                void *stream, uint64_t *ticket) {
-    const std::string who = "rt_scene_update_prims_async";
-    const int k = async_arguments(s != nullptr, s ? s->num_prims : 0u, first, count, prims_dev, true);
-    if (k == kAsyncNullScene) return fail(RT_ERR_INVALID, who + ": null scene");
-    if (k == kAsyncEmpty) return RT_OK;
-    if (k == kAsyncNullRecords) return fail(RT_ERR_INVALID, who + ": null records");
-    const int rc = refit_supported(s, who.c_str());
-    if (rc != RT_OK) return rc;
-    if (k == kAsyncRange) return fail(RT_ERR_INVALID, who + ": range outside the primitives");
-    // the light's SceneView fields are computed on the host from its record (fill_light), which this call never sees
-    if (k == kAsyncLight) return fail(RT_ERR_UNSUPPORTED, who + ": the range holds primitive 0 (the light moves through rt_scene_update_prims)");
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        return update_async(s->refit, records_of(s), PrimRecs{first, prims_dev, transforms_dev}, count, (hipStream_t)stream, 2, nullptr, 0,
-                            ticket);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, who + ": " + e.what());
-    }
-}
-
-int rt_scene_transform_triangles_async(rt_scene *s, const rt_tri_xform *ranges, uint32_t num_ranges, const float *rest_dev,
-                                       void *stream, uint64_t *ticket) {
-    const char *who = "rt_scene_transform_triangles_async";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null scene");
-    if (num_ranges == 0) return RT_OK;
-    if (!ranges) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null ranges");
-    int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    try {
-        // the table of rt_scene_transform_triangles: first[nr], prefix counts[nr + 1], matrices[16 nr]
-        std::vector<uint32_t> firsts, pre{0u}, mats;
-        std::vector<std::pair<uint32_t, uint32_t>> spans;
-        for (uint32_t r = 0; r < num_ranges; ++r) {
-            const rt_tri_xform &x = ranges[r];
-            if (x.count == 0) continue;
-            if ((uint64_t)x.first + x.count > s->num_prims)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: range " + std::to_string(r) + " outside the primitives");
-            if ((uint64_t)pre.back() + x.count > 0xffffffffull / 9u)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: too many triangles");
-            if ((rc = require_triangles(s, x.first, x.count, who)) != RT_OK) return rc;
-            firsts.push_back(x.first);
-            pre.push_back(pre.back() + x.count);
-            const uint32_t *m = reinterpret_cast<const uint32_t *>(x.M);
-            mats.insert(mats.end(), m, m + 16);
-            spans.push_back({x.first, x.count});
-        }
-        if (firsts.empty()) return RT_OK;
-        std::sort(spans.begin(), spans.end());
-        for (size_t k = 1; k < spans.size(); ++k)
-            if (spans[k - 1].first + spans[k - 1].second > spans[k].first)
-                return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: ranges overlap");
-        if (!rest_dev) return fail(RT_ERR_INVALID, "rt_scene_transform_triangles_async: null rest vertices");
-        const uint32_t nr = (uint32_t)firsts.size();
-        std::vector<uint32_t> tab(firsts);
-        tab.insert(tab.end(), pre.begin(), pre.end());
-        tab.insert(tab.end(), mats.begin(), mats.end());
-        HIP_TRY(hipSetDevice(s->device));
-        return update_xform_async(s->refit, records_of(s), tab, nr, rest_dev, (hipStream_t)stream, ticket);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_update_sync(rt_scene *s, rt_update_status *out) {
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_update_sync: null scene");
-    if (int rc = fold_updates(s); rc != RT_OK) return rc;
-    AsyncUpdates &U = s->refit.async;
-    if (out) *out = rt_update_status{U.submitted, U.applied, U.refused, U.first_refused};
-    // the earliest refusal since the previous sync is named and then forgotten
-    if (U.first_refused) (void)fail(RT_ERR_INVALID, U.first_refusal);
-    U.first_refused = 0;
-    U.first_refusal = nullptr;
-    return RT_OK;
-}
-
-// ---- the rebuild (rt_build.hip): built into fresh buffers, checked, and only then swapped in
-
-// a Rebuilt's tree becomes the scene's (the splice sets s->num_prims first): the old buffers are freed
-static void swap_in_tree(rt_scene *s, const Rebuilt &t) {
-    RefitState &R = s->refit;
-    for (void *old : {s->d_nodes, s->d_prims, R.d_slot_box, R.d_slot_of, R.d_index})
-        if (old) (void)hipFree(old);
-    s->d_nodes = t.nodes;
-    s->d_prims = t.prims;
-    R.d_slot_box = t.slot_box;
-    R.d_slot_of = t.slot_of;
-    R.d_index = t.index;
-    s->bvh.nodes_used = t.nodes_used;
-    s->bvh.depth = t.depth;
-    s->bvh.max_leaf = t.max_leaf;
-    // the host tree and the refit schedule are the old topology's: the tree is downloaded whole
-    // before its next use, the next update builds its schedule from it
-    R.topo_stale = true;
-    R.refit_ready = false;
-    for (int k = 0; k < 4; ++k) R.rebuild_stats[k] = t.stats[k];
-    // every box is the union of the finite boxes below it
-    scene_tree_fields(s, t.root_word, true, t.finite);
-}
-
-int rt_scene_rebuild(rt_scene *s, void *stream) {
-    const char *who = "rt_scene_rebuild";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_rebuild: null scene");
-    int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    // the builder's decisions are min / max over keys of the floats: a NaN box (kept from creation) has no place in them
-    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, "rt_scene_rebuild: a primitive's box is NaN or infinite");
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        Rebuilt t;
-        if ((rc = rebuild(s->refit, records_of(s), (hipStream_t)stream, t)) != RT_OK) return rc;
-        swap_in_tree(s, t);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-// ---- the splice (rt_splice.hip): triangles leave and enter; the new id space and its tree are made
-// in fresh buffers, checked, and only then swapped in
-
-// every refusal that needs no device, in the order the header lists them; *empty: nothing to do
-static int splice_arguments(const rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert,
-                            const char *who, bool *empty) {
-    const std::string w = who;
-    *empty = false;
-    uint32_t bad = 0;
-    const int k = splice_range(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, first, remove, insert, prims, &bad);
-    if (k == kSpliceLight) return fail(RT_ERR_INVALID, w + ": first = 0 (primitive 0 is the light and stays)");
-    if (k == kSpliceNull) return fail(RT_ERR_INVALID, w + ": null records");
-    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
-    if (k == kSpliceRange) return fail(RT_ERR_INVALID, w + ": range outside the primitives");
-    if (remove == 0 && insert == 0) {
-        *empty = true;
-        return RT_OK;
-    }
-    const int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
-    if (k == kSpliceKind) return fail(RT_ERR_INVALID, w + ": primitive " + std::to_string(bad) + " is not a triangle");
-    if ((uint64_t)s->num_prims - remove + insert >= (1u << 24)) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 primitives");
-    return RT_OK;
-}
-
-// a splice's own: the new id space and the host's share of it (pinfo, indices: made by the caller
-// before anything is swapped); then the tree, as after a rebuild
-static void swap_in_splice(rt_scene *s, const Rebuilt &t, std::vector<uint8_t> &pinfo, std::vector<uint32_t> &indices) {
-    RefitState &R = s->refit;
-    for (void *old : {s->d_shade, R.d_cen})
-        if (old) (void)hipFree(old);
-    s->d_shade = t.shade;
-    R.d_cen = t.cen;
-    s->view.shade = (const float4 *)s->d_shade;
-    s->num_prims = (uint32_t)pinfo.size();
-    R.pinfo.swap(pinfo);
-    s->bvh.indices.swap(indices);
-    swap_in_tree(s, t);
-}
-
-int rt_scene_splice_triangles(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims_dev, uint32_t insert,
-                              void *stream) {
-    const char *who = "rt_scene_splice_triangles";
-    bool empty = false;
-    int rc = splice_arguments(s, first, remove, prims_dev, insert, who, &empty);
-    if (rc != RT_OK || empty) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    Rebuilt t;
-    try {
-        const uint32_t n = s->num_prims - remove + insert;
-        // the host's share, made before anything is swapped: the type bytes require_triangles reads
-        // and an index array of the new size (sync_host_tree sizes its download from it)
-        RefitState &R = s->refit;
-        std::vector<uint8_t> pinfo;
-        pinfo.reserve(n);
-        pinfo.insert(pinfo.end(), R.pinfo.begin(), R.pinfo.begin() + first);
-        pinfo.insert(pinfo.end(), insert, (uint8_t)RT_TRIANGLE);
-        pinfo.insert(pinfo.end(), R.pinfo.begin() + first + remove, R.pinfo.end());
-        std::vector<uint32_t> indices(n, 0u);
-        const SpliceEdit e{first, remove, insert, prims_dev, s->num_materials};
-        if ((rc = splice(R, records_of(s), e, (hipStream_t)stream, t)) != RT_OK) return rc;
-        swap_in_splice(s, t, pinfo, indices);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        free_rebuilt(t);
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_splice_triangles_host(rt_scene *s, uint32_t first, uint32_t remove, const rt_prim *prims, uint32_t insert) {
-    bool empty = false;
-    int rc = splice_arguments(s, first, remove, prims, insert, "rt_scene_splice_triangles_host", &empty);
-    if (rc != RT_OK || empty) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    if (insert) {
-        HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-        if ((rc = grow(&s->d_scratch, &s->scratch_bytes, sizeof(rt_prim) * (size_t)insert)) != RT_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(s->d_scratch, prims, sizeof(rt_prim) * (size_t)insert, hipMemcpyHostToDevice, s->stream));
-    }
-    return rt_scene_splice_triangles(s, first, remove, insert ? (const rt_prim *)s->d_scratch : nullptr, insert, s->stream);
-}
-
-// ---- many edits in one rebuild
-
-// every refusal of rt_scene_splice_ranges that needs no device, and the sorted rows; *empty: nothing to do
-// (any_kind: rt_scene_splice_prims, the same refusals but the kind's)
-static int ranges_arguments(const rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims, const char *who,
-                            SplicePlan &plan, bool *empty, bool any_kind = false) {
-    const std::string w = who;
-    *empty = false;
-    uint32_t at = 0;
-    const int k = splice_plan(s ? s->num_prims : 0u, s ? s->refit.pinfo.data() : nullptr, edits, num_edits, prims, plan, &at, any_kind);
-    const std::string edit = ": edit " + std::to_string(at);
-    if (k == kSpliceNull) return fail(RT_ERR_INVALID, w + (edits || !num_edits ? edit + ": null records" : ": null edits"));
-    if (k == kSpliceLight) return fail(RT_ERR_INVALID, w + edit + ": first = 0 (primitive 0 is the light and stays)");
-    if (k == kSpliceSameFirst) return fail(RT_ERR_INVALID, w + edit + ": the same first as another edit (their order would be ambiguous)");
-    if (k == kSpliceOverlap) return fail(RT_ERR_INVALID, w + edit + ": its removed range overlaps another edit's");
-    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
-    if (k == kSpliceRange) return fail(RT_ERR_INVALID, w + edit + ": range outside the primitives");
-    if (k == kSpliceOk && plan.rows.empty()) {
-        *empty = true;
-        return RT_OK;
-    }
-    const int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
-    if (k == kSpliceKind) return fail(RT_ERR_INVALID, w + ": primitive " + std::to_string(at) + " is not a triangle");
-    if (k == kSpliceMany) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 primitives");
-    return RT_OK;
-}
-
-int rt_scene_splice_ranges(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims_dev, void *stream) {
-    const char *who = "rt_scene_splice_ranges";
-    Rebuilt t;
-    try {
-        SplicePlan plan;
-        bool empty = false;
-        int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty);
-        if (rc != RT_OK || empty) return rc;
-        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-        HIP_TRY(hipSetDevice(s->device));
-        RefitState &R = s->refit;
-        std::vector<uint8_t> pinfo = splice_types(R.pinfo, plan);
-        std::vector<uint32_t> indices(plan.n_new, 0u);
-        rc = splice_ranges(R, records_of(s), plan.rows.data(), (uint32_t)plan.rows.size(), plan.n_new, plan.total_insert, prims_dev,
-                           s->num_materials, (hipStream_t)stream, t);
-        if (rc != RT_OK) return rc;
-        swap_in_splice(s, t, pinfo, indices);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        free_rebuilt(t);
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_splice_ranges_host(rt_scene *s, const rt_tri_edit *edits, uint32_t num_edits, const rt_prim *prims) {
-    try {
-        SplicePlan plan;
-        bool empty = false;
-        int rc = ranges_arguments(s, edits, num_edits, prims, "rt_scene_splice_ranges_host", plan, &empty);
-        if (rc != RT_OK || empty) return rc;
-        HIP_TRY(hipSetDevice(s->device));
-        const size_t bytes = sizeof(rt_prim) * (size_t)plan.total_insert;
-        if (bytes) {
-            HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-            if ((rc = grow(&s->d_scratch, &s->scratch_bytes, bytes)) != RT_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(s->d_scratch, prims, bytes, hipMemcpyHostToDevice, s->stream));
-        }
-        return rt_scene_splice_ranges(s, edits, num_edits, bytes ? (const rt_prim *)s->d_scratch : nullptr, s->stream);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string("rt_scene_splice_ranges_host: ") + e.what());
-    }
-}
-
-static int compact_arguments(const rt_scene *s, const uint8_t *keep, const char *who) {
-    const std::string w = who;
-    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
-    if (!keep) return fail(RT_ERR_INVALID, w + ": null mask");
-    const int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if (!s->refit.boxes_finite) return fail(RT_ERR_UNSUPPORTED, w + ": a primitive's box is NaN or infinite");
-    return RT_OK;
-}
-
-int rt_scene_compact_triangles(rt_scene *s, const uint8_t *keep_dev, void *stream) {
-    const char *who = "rt_scene_compact_triangles";
-    int rc = compact_arguments(s, keep_dev, who);
-    if (rc != RT_OK) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    Rebuilt t;
-    try {
-        RefitState &R = s->refit;
-        std::vector<uint8_t> keep;
-        uint32_t n = 0;
-        if ((rc = splice_mask(R, records_of(s), keep_dev, (hipStream_t)stream, keep, &n, t)) != RT_OK || n == s->num_prims) return rc;
-        std::vector<uint8_t> pinfo;
-        pinfo.reserve(n);
-        for (uint32_t i = 0; i < s->num_prims; ++i)
-            if (keep[i]) pinfo.push_back(R.pinfo[i]);
-        std::vector<uint32_t> indices(n, 0u);
-        swap_in_splice(s, t, pinfo, indices);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        free_rebuilt(t);
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_compact_triangles_host(rt_scene *s, const uint8_t *keep) {
-    int rc = compact_arguments(s, keep, "rt_scene_compact_triangles_host");
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, s->num_prims)) != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_scratch, keep, s->num_prims, hipMemcpyHostToDevice, s->stream));
-    return rt_scene_compact_triangles(s, (const uint8_t *)s->d_scratch, s->stream);
-}
-
-// ---- primitives of any kind enter and leave: the batched routes with the kind restriction
-// lifted, and the material word alone
-
-// the commit's own share: the new side table, and the kernel family by the rule creation uses
-// (kernel_family).  A scene that gained its first cube no longer admits the wave walk: the camera-walk
-// policy falls back as rt_scene_set_camera_walk would refuse it now.  The renderers read s->ext, s->walk
-// and the view per frame, so one created before the edit takes the new family with its next frame.
-static void swap_in_kinds(rt_scene *s, Rebuilt &t) {
-    if (s->d_xprims) (void)hipFree(s->d_xprims);
-    s->d_xprims = t.xprims;
-    t.xprims = nullptr;
-    s->view.xprims = (const float4 *)s->d_xprims;
-    const std::vector<uint8_t> &types = s->refit.pinfo;
-    kernel_family(s->num_prims, [&types](uint32_t i) { return types[i] & 0x7f; }, s->ext_fixed, s->ext, s->has_cubes);
-    if (s->has_cubes && s->walk != RT_WALK_LANE) s->walk = RT_WALK_LANE;
-}
-
-int rt_scene_splice_prims(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims_dev,
-                          const float *transforms_dev, void *stream) {
-    const char *who = "rt_scene_splice_prims";
-    Rebuilt t;
-    try {
-        SplicePlan plan;
-        bool empty = false;
-        int rc = ranges_arguments(s, edits, num_edits, prims_dev, who, plan, &empty, true);
-        if (rc != RT_OK || empty) return rc;
-        if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-        HIP_TRY(hipSetDevice(s->device));
-        RefitState &R = s->refit;
-        SpliceKinds K;
-        K.T_dev = transforms_dev;
-        std::vector<uint32_t> indices(plan.n_new, 0u);
-        rc = splice_ranges(R, records_of(s), plan.rows.data(), (uint32_t)plan.rows.size(), plan.n_new, plan.total_insert, prims_dev,
-                           s->num_materials, (hipStream_t)stream, t, &K);
-        if (rc != RT_OK) return rc;
-        swap_in_splice(s, t, K.types, indices);
-        swap_in_kinds(s, t);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        free_rebuilt(t);
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_splice_prims_host(rt_scene *s, const rt_prim_edit *edits, uint32_t num_edits, const rt_prim *prims,
-                               const float *transforms) {
-    try {
-        SplicePlan plan;
-        bool empty = false;
-        int rc = ranges_arguments(s, edits, num_edits, prims, "rt_scene_splice_prims_host", plan, &empty, true);
-        if (rc != RT_OK || empty) return rc;
-        HIP_TRY(hipSetDevice(s->device));
-        const size_t count = plan.total_insert;
-        const size_t pbytes = (sizeof(rt_prim) * count + 15u) & ~(size_t)15u, tbytes = transforms ? 64 * count : 0;
-        char *base = nullptr;
-        if (count) {
-            HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-            if ((rc = grow(&s->d_scratch, &s->scratch_bytes, pbytes + tbytes)) != RT_OK) return rc;
-            base = (char *)s->d_scratch;
-            HIP_TRY(hipMemcpyAsync(base, prims, sizeof(rt_prim) * count, hipMemcpyHostToDevice, s->stream));
-            if (tbytes) HIP_TRY(hipMemcpyAsync(base + pbytes, transforms, tbytes, hipMemcpyHostToDevice, s->stream));
-        }
-        return rt_scene_splice_prims(s, edits, num_edits, (const rt_prim *)base, tbytes ? (const float *)(base + pbytes) : nullptr,
-                                     s->stream);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string("rt_scene_splice_prims_host: ") + e.what());
-    }
-}
-
-int rt_scene_compact_prims(rt_scene *s, const uint8_t *keep_dev, void *stream) {
-    const char *who = "rt_scene_compact_prims";
-    int rc = compact_arguments(s, keep_dev, who);
-    if (rc != RT_OK) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    Rebuilt t;
-    try {
-        std::vector<uint8_t> keep;
-        uint32_t n = 0;
-        SpliceKinds K;
-        if ((rc = splice_mask(s->refit, records_of(s), keep_dev, (hipStream_t)stream, keep, &n, t, &K)) != RT_OK || n == s->num_prims)
-            return rc;
-        std::vector<uint32_t> indices(n, 0u);
-        swap_in_splice(s, t, K.types, indices);
-        swap_in_kinds(s, t);
-        return RT_OK;
-    } catch (const std::exception &e) {
-        free_rebuilt(t);
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_compact_prims_host(rt_scene *s, const uint8_t *keep) {
-    int rc = compact_arguments(s, keep, "rt_scene_compact_prims_host");
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, s->num_prims)) != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_scratch, keep, s->num_prims, hipMemcpyHostToDevice, s->stream));
-    return rt_scene_compact_prims(s, (const uint8_t *)s->d_scratch, s->stream);
-}
-
-// every refusal of rt_scene_set_prim_materials that needs no device; *empty: nothing to do
-static int materials_arguments(const rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials, const char *who, bool *empty) {
-    const std::string w = who;
-    *empty = false;
-    if (!s) return fail(RT_ERR_INVALID, w + ": null scene");
-    if (count == 0) {
-        *empty = true;
-        return RT_OK;
-    }
-    if (!materials) return fail(RT_ERR_INVALID, w + ": null materials");
-    // the light's material feeds SceneView::light_mat and the kernel family
-    if (first == 0) return fail(RT_ERR_INVALID, w + ": the range holds primitive 0 (the light's material stays)");
-    if ((uint64_t)first + count > s->num_prims) return fail(RT_ERR_INVALID, w + ": range outside the primitives");
-    return RT_OK;
-}
-
-int rt_scene_set_prim_materials(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials_dev, void *stream) {
-    const char *who = "rt_scene_set_prim_materials";
-    bool empty = false;
-    int rc = materials_arguments(s, first, count, materials_dev, who, &empty);
-    if (rc != RT_OK || empty) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        return set_materials(s->refit, records_of(s), first, count, materials_dev, s->num_materials, (hipStream_t)stream);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_set_prim_materials_host(rt_scene *s, uint32_t first, uint32_t count, const int32_t *materials) {
-    bool empty = false;
-    int rc = materials_arguments(s, first, count, materials, "rt_scene_set_prim_materials_host", &empty);
-    if (rc != RT_OK || empty) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());   // the staging buffer may be in use by a batched call
-    if ((rc = grow(&s->d_scratch, &s->scratch_bytes, sizeof(int32_t) * (size_t)count)) != RT_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_scratch, materials, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, s->stream));
-    return rt_scene_set_prim_materials(s, first, count, (const int32_t *)s->d_scratch, s->stream);
-}
-
-int rt_scene_rebuild_stats(const rt_scene *s, uint32_t out[4]) {
-    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_rebuild_stats: null argument");
-    for (int k = 0; k < 4; ++k) out[k] = s->refit.rebuild_stats[k];
-    return RT_OK;
-}
-
-// ---- the refit schedule ahead of the first update (rt_plan.hip)
-
-int rt_scene_prepare_updates(rt_scene *s, void *stream) {
-    const char *who = "rt_scene_prepare_updates";
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_prepare_updates: null scene");
-    const int rc = refit_supported(s, who);
-    if (rc != RT_OK) return rc;
-    if (int frc = fold_updates(s); frc != RT_OK) return frc;   // the async updates first (rt_scene_update_sync)
-    HIP_TRY(hipSetDevice(s->device));
-    try {
-        return prepare_updates(s->refit, records_of(s), (hipStream_t)stream);
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, std::string(who) + ": " + e.what());
-    }
-}
-
-int rt_scene_update_plan_info(const rt_scene *s, uint32_t out[8]) {
-    if (!s || !out) return fail(RT_ERR_INVALID, "rt_scene_update_plan_info: null argument");
-    if (int frc = fold_updates(const_cast<rt_scene *>(s)); frc != RT_OK) return frc;
-    const RefitState &R = s->refit;
-    const PlanInfo none{}, &p = R.refit_ready ? R.plan_info : none;
-    out[0] = R.refit_ready ? 1u : 0u;
-    out[1] = p.route;
-    out[2] = R.refit_ready ? R.plan.ntreelets : 0u;
-    out[3] = R.refit_ready && R.plan.has_top ? 1u : 0u;
-    out[4] = p.list_len;
-    out[5] = p.lvl_len;
-    out[6] = p.top_nodes;
-    out[7] = p.launches;
-    return RT_OK;
-}
-
-int rt_scene_copy_update_plan(const rt_scene *s, uint32_t *list, uint32_t *lvl, uint32_t *grp) {
-    if (!s) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: null scene");
-    if (int frc = fold_updates(const_cast<rt_scene *>(s)); frc != RT_OK) return frc;
-    const RefitState &R = s->refit;
-    if (!R.refit_ready) return fail(RT_ERR_INVALID, "rt_scene_copy_update_plan: no schedule is ready (rt_scene_prepare_updates)");
-    HIP_TRY(hipSetDevice(s->device));
-    // the schedule's builder and every update block, so the arrays are settled
-    if (list) HIP_TRY(hipMemcpy(list, R.d_list, sizeof(uint32_t) * R.plan_info.list_len, hipMemcpyDeviceToHost));
-    if (lvl) HIP_TRY(hipMemcpy(lvl, R.d_lvl, sizeof(uint32_t) * R.plan_info.lvl_len, hipMemcpyDeviceToHost));
-    if (grp) HIP_TRY(hipMemcpy(grp, R.d_grp, sizeof(uint32_t) * ((size_t)R.plan.ntreelets + 2), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

@@ -1,4 +1,4 @@
-// rt_internal.h -- host-side internals shared by rt_host.cpp, rt_scene_pack.cpp and rt_device.hip.
+// rt_internal.h -- host-side internals shared by rt_host.cpp, rt_scene_pack.cpp, rt_device.hip and rt_scene_edit.hip.
 #pragma once
 #include <string>
 #include <vector>

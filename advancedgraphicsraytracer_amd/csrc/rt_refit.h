@@ -1,6 +1,6 @@
 // rt_refit.h -- in-place updates: the refit plan of a scene's tree (built in rt_scene_pack.cpp),
 // the update state a scene keeps, and the one host path of rt_refit.hip that every update entry
-// point of rt_device.hip takes (rt_scene_update_triangles, rt_scene_update_prims,
+// point of rt_scene_edit.hip takes (rt_scene_update_triangles, rt_scene_update_prims,
 // rt_scene_transform_triangles), with its stream-ordered form (update_async; the rt_scene_*_async
 // entry points and rt_scene_update_sync).  The per-lane text is in rt_update.h.
 #pragma once
@@ -67,7 +67,7 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 //            with its device twin and the event of the update that read it.  A slot is taken again
 //            kXformSlots updates later; the call waits for its event only then.
 // The host's counts are folded from the block by drain_updates; kinds holds, per ticket since the
-// last fold, which entry point it came from (its refusal text).
+// last fold, which entry point it came from (update_async's `kind`).
 constexpr int kXformSlots = 8;
 struct XformSlot {
     void *host = nullptr, *dev = nullptr;
@@ -81,7 +81,7 @@ struct AsyncUpdates {
     bool issued = false;            // an async update was enqueued since the last fold
     uint64_t submitted = 0, applied = 0, refused = 0, first_refused = 0;
     uint64_t folded = 0;            // tickets <= this are folded into the counts
-    const char *first_refusal = nullptr;
+    int first_kind = -1;            // ... of the ticket first_refused (-1: none)
     std::vector<uint8_t> kinds;     // ticket folded + 1 + k -> index into the refusal texts
     XformSlot ring[kXformSlots];
     uint32_t ring_next = 0;
@@ -148,22 +148,23 @@ struct UpdateCopy {
 };
 // One in-place update of n lanes of `src` (TriVerts, TriXform or PrimRecs over device memory) on
 // `st`: waits for the frames still reading the scene, builds the plan on the scene's first update,
-// runs the check and reads its flag back -- a refusal (RT_ERR_INVALID, `refusal`) has written
+// runs the check and reads its flag back -- a refusal (RT_ERR_INVALID, "<who>: <refusal>") has written
 // nothing --, then the write, the refit of every treelet and of the nodes above the cut, and the
 // new root box.  Blocks.  *finite = every box of the tree is finite now.
 template <class Src>
-int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *refusal,
+int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *who, const char *refusal,
            const UpdateCopy *copies, int ncopies, bool *finite);
 // the same for ranges of triangles moved by one matrix each; tab = first[nr], prefix counts[nr + 1],
 // matrices[16 nr], uploaded to the scene's range table
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
-                 hipStream_t st, const char *refusal, bool *finite);
+                 hipStream_t st, const char *who, const char *refusal, bool *finite);
 // The stream-ordered form of update(): everything is enqueued on `st` and the call returns.  Order:
 // wait for the scene's previous async update (any stream), the copies, the check (its flag stays on
 // the device), the gated write and refits, the settle step under `ticket` (= ++submitted), the
 // scene's event.  Blocks only to build a missing schedule (ensure_refit) and to create the status
-// block on a scene's first call.  `kind` indexes kRefusals.  *ticket_out may be null.
-extern const char *const kRefusals[3];
+// block on a scene's first call.  `kind`: which entry point it is (0 rt_scene_update_triangles_async,
+// 1 rt_scene_transform_triangles_async, 2 rt_scene_update_prims_async), kept per ticket for the text of a
+// refusal (kRefusals, rt_scene_edit.hip).  *ticket_out may be null.
 template <class Src>
 int update_async(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, int kind,
                  const UpdateCopy *copies, int ncopies, uint64_t *ticket_out);

@@ -204,7 +204,7 @@ void free_refit(RefitState &R) {
 }
 
 template <class Src>
-int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *refusal,
+int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hipStream_t st, const char *who, const char *refusal,
            const UpdateCopy *copies, int ncopies, bool *finite) {
     HIP_TRY(hipDeviceSynchronize());   // frames still reading the scene on any stream
     int rc = ensure_refit(R, S, st);
@@ -220,7 +220,7 @@ int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hip
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return fail(RT_ERR_INVALID, refusal);
+    if (bad) return fail(RT_ERR_INVALID, std::string(who) + ": " + refusal);
     hipLaunchKernelGGL(k_write<Src>, grid, block, 0, st, A, src, n);
     // the treelets, then (a second launch) the nodes above the cut
     hipLaunchKernelGGL(k_refit_treelets, dim3(R.plan.ntreelets), dim3(256), 0, st, A);
@@ -235,18 +235,12 @@ int update(RefitState &R, const SceneRecords &S, const Src &src, uint32_t n, hip
     for (float f : {root[0].x, root[0].y, root[0].z, root[0].w, root[1].x, root[1].y}) *finite = *finite && std::isfinite(f);
     return RT_OK;
 }
-template int update<TriVerts>(RefitState &, const SceneRecords &, const TriVerts &, uint32_t, hipStream_t, const char *,
+template int update<TriVerts>(RefitState &, const SceneRecords &, const TriVerts &, uint32_t, hipStream_t, const char *, const char *,
                               const UpdateCopy *, int, bool *);
-template int update<PrimRecs>(RefitState &, const SceneRecords &, const PrimRecs &, uint32_t, hipStream_t, const char *,
+template int update<PrimRecs>(RefitState &, const SceneRecords &, const PrimRecs &, uint32_t, hipStream_t, const char *, const char *,
                               const UpdateCopy *, int, bool *);
 
 // ---- the stream-ordered path
-
-const char *const kRefusals[3] = {
-    "rt_scene_update_triangles_async: a vertex is NaN or infinite",
-    "rt_scene_transform_triangles_async: a transformed vertex is NaN or infinite",
-    "rt_scene_update_prims_async: a record's type or material is not the scene's, or a field, transform or box is NaN or infinite",
-};
 
 int drain_updates(RefitState &R, uint64_t *applied_new) {
     AsyncUpdates &U = R.async;
@@ -258,7 +252,7 @@ int drain_updates(RefitState &R, uint64_t *applied_new) {
     if (h.first_refused) {
         if (!U.first_refused) {
             U.first_refused = h.first_refused;
-            U.first_refusal = kRefusals[U.kinds[(size_t)(h.first_refused - U.folded - 1u)]];
+            U.first_kind = U.kinds[(size_t)(h.first_refused - U.folded - 1u)];
         }
         HIP_TRY(hipMemset((char *)U.status + offsetof(UpdateStatus, first_refused), 0, sizeof(uint64_t)));
     }
@@ -367,7 +361,7 @@ int update_xform_async(RefitState &R, const SceneRecords &S, const std::vector<u
 }
 
 int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_t> &tab, uint32_t nr, const float *rest_dev,
-                 hipStream_t st, const char *refusal, bool *finite) {
+                 hipStream_t st, const char *who, const char *refusal, bool *finite) {
     const size_t need = sizeof(uint32_t) * tab.size();
     int rc = grow(&R.d_ranges, &R.ranges_bytes, need);
     if (rc != RT_OK) return rc;
@@ -379,7 +373,7 @@ int update_xform(RefitState &R, const SceneRecords &S, const std::vector<uint32_
     src.rest = rest_dev;
     // the table has left the host vector at update's synchronise after the check
     const UpdateCopy table{R.d_ranges, tab.data(), need, hipMemcpyHostToDevice};
-    return update(R, S, src, tab[2 * (size_t)nr], st, refusal, &table, 1, finite);
+    return update(R, S, src, tab[2 * (size_t)nr], st, who, refusal, &table, 1, finite);
 }
 
 }  // namespace rt

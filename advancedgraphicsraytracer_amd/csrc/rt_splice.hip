@@ -22,7 +22,7 @@
 // The builder (build_tree of rt_build.hip) then runs over the new id space with the identity as its
 // old slot map.  Nothing is handed from one workgroup to another inside a launch: launch boundaries
 // order check -> gather -> build.  The scene's own buffers are only read; the caller swaps the new
-// ones in when everything succeeded (rt_scene_splice_triangles in rt_device.hip).
+// ones in when everything succeeded (rt_scene_splice_triangles in rt_scene_edit.hip).
 #include "rt_refit.h"
 #include "rt_splice.h"
 

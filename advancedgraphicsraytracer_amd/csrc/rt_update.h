@@ -4,13 +4,19 @@
 // One text for gfx950 and for the host, like rt_records.h and under the same -ffp-contract=off:
 // the kernels only supply the lane index and the barrier between heights, so a stand-alone host
 // program runs check -> write -> refit end to end with tid = 0, stride = 1
-// (tests/cpp/update_host.cpp, tests/cpp/prim_records_host.cpp).  No std:: algorithm.
+// (tests/cpp/update_host.cpp, tests/cpp/prim_records_host.cpp).  No std:: algorithm in what a lane
+// runs; the host's making of rt_scene_transform_triangles' range table (xform_table) is marked as such.
 //
 // A *source* maps lane i of a call to "primitive id + its new geometry":
 //   ok(A, i)     would the write of lane i produce a finite, admissible record?  Writes nothing;
 //   write(A, i)  the leaf-slot record, the shading record, the slot box (and, for a cube or a quad,
 //                the side-table entry) of that primitive.
 #pragma once
+#include <algorithm>
+#include <cstring>
+#include <utility>
+#include <vector>
+
 #include "rt_records.h"
 
 namespace rt {
@@ -78,6 +84,46 @@ RT_HD uint32_t range_of(const uint32_t *pre, uint32_t nr, uint32_t i) {
         else hi = mid;
     }
     return lo;
+}
+// The host's part of rt_scene_transform_triangles, shared by its blocking and its stream-ordered entry
+// point and the stand-alone program: the refusals that need no device, and the table.  Empty ranges are
+// dropped; per kept range, in the caller's order: inside the primitives, at most 0xffffffff / 9 triangles
+// so far (lane i reads rest[9 i] with 32-bit arithmetic), triangles all (ptype[id] & 0x7f, RefitState::pinfo;
+// null: not looked at); then no triangle in two ranges, and the rest vertices last.  *where: the range
+// (caller's index) or the primitive refused.  tab = first[nr] | pre[nr + 1] | M[16 nr].
+enum { kXformOk = 0, kXformEmpty, kXformRange, kXformMany, kXformKind, kXformOverlap, kXformNullRest };
+inline int xform_table(uint32_t num_prims, const uint8_t *ptype, const rt_tri_xform *ranges, uint32_t num_ranges, const void *rest,
+                       std::vector<uint32_t> &tab, uint32_t *nr, uint32_t *where) {
+    std::vector<uint32_t> kept;   // the non-empty ranges
+    std::vector<std::pair<uint32_t, uint32_t>> spans;
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < num_ranges; ++r) {
+        const rt_tri_xform &x = ranges[r];
+        if (x.count == 0) continue;
+        *where = r;
+        if ((uint64_t)x.first + x.count > num_prims) return kXformRange;
+        if (total + x.count > 0xffffffffull / 9u) return kXformMany;
+        for (uint32_t id = x.first; ptype && id < x.first + x.count; ++id)
+            if ((ptype[id] & 0x7f) != RT_TRIANGLE) { *where = id; return kXformKind; }
+        kept.push_back(r);
+        spans.push_back({x.first, x.count});
+        total += x.count;
+    }
+    if (kept.empty()) return kXformEmpty;
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); ++k)
+        if (spans[k - 1].first + spans[k - 1].second > spans[k].first) return kXformOverlap;
+    if (!rest) return kXformNullRest;
+    const size_t n = kept.size();
+    tab.assign(n + (n + 1) + 16 * n, 0u);
+    for (size_t k = 0; k < n; ++k) {
+        const rt_tri_xform &x = ranges[kept[k]];
+        tab[k] = x.first;
+        tab[n + k + 1] = tab[n + k] + x.count;
+        std::memcpy(&tab[2 * n + 1 + 16 * k], x.M, sizeof(x.M));
+    }
+    *nr = (uint32_t)n;
+    return kXformOk;
 }
 struct TriXform {
     XformRanges R;
@@ -211,10 +257,11 @@ struct UpdateStatus {
     uint64_t applied, refused;   // updates since the scene was created
     uint64_t first_refused;   // ticket of the earliest refusal since the host last read the block (0: none)
 };
-// What the stream-ordered entry points refuse without the device or the records' contents, in the
-// blocking calls' order (the scene-kind refusals -- SBVH, RT_PT_QUADS -- come between kAsyncNullRecords
-// and kAsyncRange).  light_stays: rt_scene_update_prims_async, where primitive 0 moves through the
-// blocking call alone.
+// What rt_scene_update_triangles and rt_scene_update_prims, blocking or stream-ordered, refuse without
+// the device or the records' contents, in order (the scene-kind refusals -- SBVH, RT_PT_QUADS -- come
+// between kAsyncNullRecords and kAsyncRange).  Named for the stream-ordered forms it was written for; the
+// blocking and the _host forms take their refusals from it too.  light_stays: rt_scene_update_prims_async,
+// where primitive 0 moves through the blocking call alone.
 enum { kAsyncOk = 0, kAsyncNullScene, kAsyncEmpty, kAsyncNullRecords, kAsyncRange, kAsyncLight };
 RT_HD int async_arguments(bool scene, uint32_t num_prims, uint32_t first, uint32_t count, const void *recs, bool light_stays) {
     if (!scene) return kAsyncNullScene;

@@ -11,6 +11,7 @@
 // the tree that rt_bvh_refit_host gives.
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "scene_util.h"
@@ -182,7 +183,7 @@ static int tri_verts(const SceneSource &teapot, const ScenePack &at0, uint32_t f
 
 static int tri_xform(const SceneSource &teapot, const ScenePack &at0, uint32_t first) {
     // three ranges in non-ascending order, counts 1, 256 and 257, a matrix each
-    struct Range { uint32_t first, count; float M[16]; } R[3] = {{first + 600, 257, {}}, {first + 10, 1, {}}, {first + 100, 256, {}}};
+    rt_tri_xform R[3] = {{first + 600, 257, {}}, {first + 10, 1, {}}, {first + 100, 256, {}}};
     float Tr[16], Ro[16];
     mat4_translate(0.25f, -0.5f, 0.125f, Tr);
     rt_mat4_rotate(1, 0.7f, Ro);
@@ -192,15 +193,18 @@ static int tri_xform(const SceneSource &teapot, const ScenePack &at0, uint32_t f
     rt_mat4_rotate(2, 0.2f, Ro);
     mat4_mul(Ro, Tr, R[2].M);
     for (int i = 0; i < 12; ++i) R[2].M[i] *= (i % 4 == 3) ? 1.0f : 1.5f;   // and a scale
-    // the table as rt_scene_transform_triangles lays it out; the rest vertices back to back
-    std::vector<uint32_t> firsts, pre{0u};
-    std::vector<float> mats, rest;
-    for (const Range &r : R) {
-        firsts.push_back(r.first);
-        pre.push_back(pre.back() + r.count);
-        mats.insert(mats.end(), r.M, r.M + 16);
+    // the rest vertices back to back; the table as rt_scene_transform_triangles makes it (xform_table)
+    std::vector<float> rest;
+    for (const rt_tri_xform &r : R)
         for (uint32_t i = 0; i < r.count; ++i) rest.insert(rest.end(), teapot.prims[r.first + i].v, teapot.prims[r.first + i].v + 9);
-    }
+    std::vector<uint32_t> tab;
+    uint32_t nr = 0, at = 0;
+    CHECK(xform_table((uint32_t)teapot.prims.size(), at0.pinfo.data(), R, 3, rest.data(), tab, &nr, &at) == kXformOk);
+    CHECK(nr == 3 && tab.size() == 3u + 4u + 48u);
+    const std::vector<uint32_t> firsts(tab.begin(), tab.begin() + 3), pre(tab.begin() + 3, tab.begin() + 7);
+    std::vector<float> mats(48);
+    std::memcpy(mats.data(), &tab[7], sizeof(float) * 48);
+    for (int r = 0; r < 3; ++r) CHECK(firsts[r] == R[r].first && std::memcmp(&mats[16 * r], R[r].M, sizeof(R[r].M)) == 0);
     const uint32_t total = pre.back();
     CHECK(total == 514 && rest.size() == 9u * total);
     const TriXform src{XformRanges{firsts.data(), pre.data(), mats.data(), 3}, rest.data()};
@@ -258,6 +262,65 @@ static int tri_xform(const SceneSource &teapot, const ScenePack &at0, uint32_t f
     again.pack = at0;
     CHECK(again.prepare(PackOptions()));
     CHECK(equal(still, again));                // a check writes nothing
+    return 0;
+}
+
+// xform_table, the host's part of rt_scene_transform_triangles (blocking and stream-ordered): its
+// refusals in their order and the table's layout, on eight primitives -- the light, six triangles (one
+// with the sticky bit of RefitState::pinfo set), a sphere
+static int xform_tables() {
+    const uint8_t T = RT_TRIANGLE, ptype[8] = {RT_SPHERE, T, T, (uint8_t)(T | 0x80), T, T, T, RT_SPHERE};
+    const float rest[9] = {};
+    auto range = [](uint32_t first, uint32_t count, float seed) {
+        rt_tri_xform x{first, count, {}};
+        for (int k = 0; k < 16; ++k) x.M[k] = seed + 0.25f * (float)k;
+        return x;
+    };
+    std::vector<uint32_t> tab;
+    uint32_t nr = 77, at = 77;
+    auto run = [&](uint32_t n, const uint8_t *types, const std::vector<rt_tri_xform> &r, const void *rest_) {
+        tab.assign(1, 0xdeadbeefu);
+        nr = at = 77;
+        return xform_table(n, types, r.data(), (uint32_t)r.size(), rest_, tab, &nr, &at);
+    };
+    // three ranges, one of them empty: it is dropped, and the layout is first | pre | M
+    const std::vector<rt_tri_xform> three = {range(4, 2, 1.0f), range(5, 0, 2.0f), range(1, 3, 3.0f)};
+    CHECK(run(8, ptype, three, rest) == kXformOk && nr == 2);
+    std::vector<uint32_t> want = {4, 1, 0, 2, 5};
+    want.resize(5 + 32);
+    std::memcpy(&want[5], three[0].M, 64);
+    std::memcpy(&want[5 + 16], three[2].M, 64);
+    CHECK(same_bytes(tab, want) && tab[2 * nr] == 5);                        // pre[nr]: every triangle of the call
+    // adjacent ranges in either order; an overlap of one triangle in either order
+    CHECK(run(8, ptype, {range(1, 2, 0), range(3, 2, 0)}, rest) == kXformOk && nr == 2 && tab[0] == 1 && tab[1] == 3);
+    CHECK(run(8, ptype, {range(3, 2, 0), range(1, 2, 0)}, rest) == kXformOk && nr == 2 && tab[0] == 3 && tab[1] == 1);
+    CHECK(run(8, ptype, {range(1, 3, 0), range(3, 2, 0)}, rest) == kXformOverlap);
+    CHECK(run(8, ptype, {range(3, 2, 0), range(1, 3, 0)}, rest) == kXformOverlap);
+    CHECK(tab.size() == 1 && tab[0] == 0xdeadbeefu && nr == 77);             // a refusal leaves the table alone
+    // one past the primitives: that range's index in the caller's numbering, empty ranges counted
+    CHECK(run(8, ptype, {range(1, 1, 0), range(2, 0, 0), range(7, 2, 0)}, rest) == kXformRange && at == 2);
+    CHECK(run(8, ptype, {range(0xffffffffu, 2, 0)}, rest) == kXformRange && at == 0);   // first + count past 2^32
+    // the sphere's id; the range before the kind, the kind before the overlap
+    CHECK(run(8, ptype, {range(1, 1, 0), range(5, 3, 0)}, rest) == kXformKind && at == 7);
+    CHECK(run(8, ptype, {range(0, 2, 0)}, rest) == kXformKind && at == 0);
+    CHECK(run(8, ptype, {range(5, 4, 0)}, rest) == kXformRange && at == 0);
+    CHECK(run(8, ptype, {range(1, 3, 0), range(3, 5, 0)}, rest) == kXformKind && at == 7);
+    // 0xffffffff / 9 triangles at most (lane i reads rest[9 i]): counts that exceed it only in sum, on a
+    // scene without type bytes
+    const uint32_t cap = 477218588u;
+    CHECK(cap == 0xffffffffu / 9u && (uint64_t)9u * cap <= 0xffffffffull && (uint64_t)9u * (cap + 1u) > 0xffffffffull);
+    CHECK(run(0xffffffffu, nullptr, {range(0, 300000000u, 0), range(300000000u, cap - 300000000u, 0)}, rest) == kXformOk);
+    CHECK(nr == 2 && tab[2 * nr] == cap);
+    CHECK(run(0xffffffffu, nullptr, {range(0, 300000000u, 0), range(300000000u, cap - 300000000u + 1u, 0)}, rest) == kXformMany && at == 1);
+    CHECK(run(0xffffffffu, nullptr, {range(0, cap + 1u, 0)}, rest) == kXformMany && at == 0);
+    CHECK(run(0xffffffffu, nullptr, {range(5, 0xffffffffu, 0)}, rest) == kXformRange);   // the range before the cap
+    // nothing to do, null rest vertices or not; null rest vertices are what is refused last
+    CHECK(run(8, ptype, {}, nullptr) == kXformEmpty && run(8, ptype, {range(3, 0, 0), range(9, 0, 0)}, nullptr) == kXformEmpty);
+    CHECK(run(8, ptype, {range(3, 0, 0)}, rest) == kXformEmpty);
+    CHECK(run(8, ptype, {range(3, 2, 0), range(1, 2, 0)}, nullptr) == kXformNullRest);
+    CHECK(run(8, ptype, {range(3, 2, 0), range(1, 3, 0)}, nullptr) == kXformOverlap);
+    CHECK(run(8, ptype, {range(6, 2, 0)}, nullptr) == kXformKind && at == 7);
+    CHECK(run(8, ptype, {range(7, 2, 0)}, nullptr) == kXformRange);
     return 0;
 }
 
@@ -323,7 +386,7 @@ int main(int argc, char **argv) {
     CHECK(ntri == 1026);
     ScenePack at0;
     CHECK(pack(teapot.prims, teapot.materials, nullptr, nullptr, at0) == RT_OK);
-    if (plans(teapot) || tri_verts(teapot, at0, first, ntri) || tri_xform(teapot, at0, first) || refusals(teapot, at0, first) ||
+    if (plans(teapot) || tri_verts(teapot, at0, first, ntri) || xform_tables() || tri_xform(teapot, at0, first) || refusals(teapot, at0, first) ||
         prim_refusals())
         return 1;
     std::printf("update_host ok\n");
