@@ -18,7 +18,9 @@ struct DevMaterial {
     float c0[3], c1[3];
     float ior, diffuse, specular;
     uint32_t tex_off, tex_w, tex_h;   // TextureMaterial: texels at SceneView::tex + tex_off
+    uint32_t pad_[2];                 // 64 bytes: a material is four aligned float4 (hit_surface_whole)
 };
+static_assert(sizeof(DevMaterial) == 64, "DevMaterial is read as four float4");
 
 struct SceneView {
     const float4 *__restrict__ nodes;   // 2 float4 per node

@@ -43,6 +43,25 @@ namespace RT_KNS {
 // the hot kernels carry none of their registers
 constexpr bool kExt = RT_EXT != 0;
 
+// Phase stamps, diagnostic builds only (tools/build_variant.sh NAME -DRT_FRAME_PHASES, read by
+// tools/frame_phases.py): the first active lane of a wave stores s_memtime at six points of the
+// primary+shadow frame -- [0] wave start, [1] head done (ray ready), [2] camera traversal done,
+// [3] shading done (shadow ray ready), [4] shadow traversal done, [5] wave end -- into
+// rt_frame_phase_buf[unit * 8 + k] with ordinary vector stores.  Waves past kFramePhaseWaves are not
+// recorded; a phase a wave never reaches stays 0.  The production build compiles none of it.
+#ifdef RT_FRAME_PHASES
+constexpr uint32_t kFramePhaseWaves = 65536;
+__device__ unsigned long long rt_frame_phase_buf[kFramePhaseWaves * 8u];
+__device__ __forceinline__ void frame_phase(uint32_t k) {
+    const uint32_t unit = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    const uint32_t first = (uint32_t)__builtin_ctzll(__ballot(1));
+    if (unit < kFramePhaseWaves && (threadIdx.x & 63u) == first) rt_frame_phase_buf[unit * 8u + k] = t;
+}
+#else
+__device__ __forceinline__ void frame_phase(uint32_t) {}
+#endif
+
 
 struct DRay {
     f3 O, D, rD;
@@ -400,8 +419,7 @@ __device__ __forceinline__ void finish_uv(const SceneView &S, DRay &r) {
 
 // Scene::GetNormal (template/scene.h:489-497) of the hit primitive at I, not yet flipped:
 // Primitive::GetNormal (Primitive.h:284-314)
-__device__ __forceinline__ f3 prim_normal(const SceneView &S, int obj, f3 I) {
-    const float4 s0 = S.shade[2 * obj], s1 = S.shade[2 * obj + 1];
+__device__ __forceinline__ f3 prim_normal(const SceneView &S, float4 s0, float4 s1, f3 I) {
     const uint32_t type = __float_as_uint(s1.x);
     if (type == T_SPH) return (I - mk(s0.x, s0.y, s0.z)) * s1.y;
     if (!kExt || type != T_CUBE) return mk(s0.x, s0.y, s0.z);
@@ -419,6 +437,9 @@ __device__ __forceinline__ f3 prim_normal(const SceneView &S, int obj, f3 I) {
     if (e5 < minDist) minDist = e5, N = mk(0, 0, 1);
     return tvec_rows(x[3], x[4], x[5], N);
 }
+__device__ __forceinline__ f3 prim_normal(const SceneView &S, int obj, f3 I) {
+    return prim_normal(S, S.shade[2 * obj], S.shade[2 * obj + 1], I);
+}
 
 // Scene::GetNormal (flipped against the ray) and Scene::GetMaterial of a hit; a
 // TextureMaterial also needs the hit's u, v (deferred by the traversal, finish_uv)
@@ -426,6 +447,29 @@ __device__ __forceinline__ const DevMaterial &hit_surface(const SceneView &S, DR
     N = prim_normal(S, ray.obj, I);
     if (dot(N, ray.D) > 0) N = -N;
     const DevMaterial &m = S.mats[__float_as_int(S.shade[2 * ray.obj].w)];
+    if (kExt && m.kind == RT_TEXTURE) finish_uv(S, ray);
+    return m;
+}
+
+// hit_surface with whole records (the single-sample frame kernel): both float4 of the hit's shade
+// record in one request, the material index taken from it, then the material's first 48 bytes
+// (kind .. tex_off; the extension build: all 64) in one request -- two dependent round trips.  Field
+// by field the compiler narrows each load to what its first user needs and fetches the rest where
+// the next user stands: shade .xyz + type, shade .w again, flag, kind, colour -- five trips.  The
+// empty asm keeps each group whole and where it is written.
+__device__ __forceinline__ DevMaterial hit_surface_whole(const SceneView &S, DRay &ray, f3 I, f3 &N) {
+    float4 s0 = S.shade[2 * ray.obj], s1 = S.shade[2 * ray.obj + 1];
+    asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s0.z), "+v"(s0.w), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w));
+    static_assert(sizeof(DevMaterial) == 64, "a material is four float4");
+    const float4 *mp = reinterpret_cast<const float4 *>(S.mats + __float_as_int(s0.w));
+    float4 q[4] = {mp[0], mp[1], mp[2], kExt ? mp[3] : make_float4(0, 0, 0, 0)};
+    asm volatile("" : "+v"(q[0].x), "+v"(q[0].y), "+v"(q[0].z), "+v"(q[0].w), "+v"(q[1].x), "+v"(q[1].y), "+v"(q[1].z),
+                      "+v"(q[1].w), "+v"(q[2].x), "+v"(q[2].y), "+v"(q[2].z), "+v"(q[2].w));
+    if constexpr (kExt) asm volatile("" : "+v"(q[3].x), "+v"(q[3].y));
+    DevMaterial m;
+    __builtin_memcpy(&m, q, sizeof(m));
+    N = prim_normal(S, s0, s1, I);
+    if (dot(N, ray.D) > 0) N = -N;
     if (kExt && m.kind == RT_TEXTURE) finish_uv(S, ray);
     return m;
 }
@@ -1006,11 +1050,22 @@ __device__ __forceinline__ f3 light_point(const SceneView &S, uint32_t &seed) {
 }
 
 // Renderer::NextEventDirectIllumination, renderer.h:44-75 (light = prim 0, a sphere)
-template <class TR>
+// EARLY (the single-sample frame kernel): the light's area and, in the core build, its colour are
+// requested before the shadow ray is traced, not inside its result's branch
+template <class TR, bool EARLY = false>
 __device__ __forceinline__ f3 nee(const SceneView &S, const TR &T, f3 I, f3 N, f3 BRDF, uint32_t &seed,
                                   uint32_t &nshadow) {
     f3 Il = light_point(S, seed);
-    const float area = S.light_area;                                   // GetArea, Primitive.h:450-468
+    float area = S.light_area;                                         // GetArea, Primitive.h:450-468
+    f3 lc0 = mk(0, 0, 0);
+    if constexpr (EARLY) {
+        if constexpr (!kExt) {
+            const DevMaterial &lm = S.mats[S.light_mat];
+            lc0 = mk(lm.c0[0], lm.c0[1], lm.c0[2]);
+            asm volatile("" : "+v"(lc0.x), "+v"(lc0.y), "+v"(lc0.z));
+        }
+        asm volatile("" : "+v"(area));
+    }
     f3 L = Il - I;
     float dist = length(L);
     L = L / dist;
@@ -1019,6 +1074,7 @@ __device__ __forceinline__ f3 nee(const SceneView &S, const TR &T, f3 I, f3 N, f
     if (dot(Nl, L) > 0) Nl = -Nl;                                      // Scene::GetNormal flip
     float dotNL = dot(N, L), dotNlL = dot(Nl, -L);
     f3 Ld = mk(0, 0, 0);
+    frame_phase(3);
     if (dotNL > 0 && dotNlL > 0) {
         DRay sh = make_ray(I, L, dist - 2.0f * kEPS);
         ++nshadow;
@@ -1027,10 +1083,11 @@ __device__ __forceinline__ f3 nee(const SceneView &S, const TR &T, f3 I, f3 N, f
             float lightPDF = 1.0f / solid;
             const DevMaterial &lm = S.mats[S.light_mat];                // GetLightColor(0, toLight)
             // the core build only sees Light / Diffuse / Mirror / DSMix light materials (colour c0)
-            const f3 lc = !kExt ? mk(lm.c0[0], lm.c0[1], lm.c0[2]) : mat_color(S, lm, sh, sh.O + sh.t * sh.D);
+            const f3 lc = !kExt ? (EARLY ? lc0 : mk(lm.c0[0], lm.c0[1], lm.c0[2])) : mat_color(S, lm, sh, sh.O + sh.t * sh.D);
             Ld = (lc * BRDF) * (dotNL / lightPDF);
         }
     }
+    frame_phase(4);
     return Ld;
 }
 
@@ -1039,7 +1096,9 @@ __device__ __forceinline__ f3 nee(const SceneView &S, const TR &T, f3 I, f3 N, f
 // so the float evaluation order is the reference's.
 // CAMWAVE: 0 camera rays take closest_hit, 1 closest_hit_primary (the wave walk where the scene
 // asks for it), 2 the same with the walk checks compiled in (k_render_walkcheck)
-template <int MAXD, bool TEX_SKY, class TR, int CAMWAVE = 0>
+// WHOLE: the hit's shade record and material are fetched whole (hit_surface_whole) and NEE's light
+// fields early -- the single-sample frame kernel
+template <int MAXD, bool TEX_SKY, class TR, int CAMWAVE = 0, bool WHOLE = false>
 __device__ f3 trace_path(const SceneView &S, const TR &T, DRay ray, int depth, uint32_t &seed,
                          uint32_t &nshadow, uint32_t &nbounce, bool lastSpec = true) {
     f3 lv_mul[MAXD], lv_add[MAXD];
@@ -1055,10 +1114,13 @@ __device__ f3 trace_path(const SceneView &S, const TR &T, DRay ray, int depth, u
         } else {
             closest_hit(S, T, ray);
         }
+        frame_phase(2);
         if (ray.obj == -1) { term = sky_color<TEX_SKY>(S, ray.D); break; }
         f3 I = ray.O + ray.t * ray.D;
         f3 N;
-        const DevMaterial &m = hit_surface(S, ray, I, N);
+        DevMaterial m_whole;
+        if constexpr (WHOLE) m_whole = hit_surface_whole(S, ray, I, N);
+        const DevMaterial &m = WHOLE ? m_whole : hit_surface(S, ray, I, N);
         if (m.flag == F_LIGHT) { term = lastSpec ? mk(m.c0[0], m.c0[1], m.c0[2]) : mk(0, 0, 0); break; }
         const bool last = MAXD == 1 || d == 1;   // MAXD 1: the bounce ray is never traced
         DRay out;
@@ -1066,7 +1128,7 @@ __device__ f3 trace_path(const SceneView &S, const TR &T, DRay ray, int depth, u
         f3 albedo = mat_color(S, m, ray, I);
         if (m.flag == F_DIFFUSE || (m.flag == F_MIX && !spec)) {
             f3 BRDF = albedo * kINVPI;
-            lv_add[levels] = nee(S, T, I, N, BRDF, seed, nshadow);
+            lv_add[levels] = nee<TR, WHOLE>(S, T, I, N, BRDF, seed, nshadow);
             lv_mul[levels] = BRDF;
             lv_c[levels] = last ? 0.0f : dot(N, out.D);
             lv_diff[levels] = true;
@@ -1354,7 +1416,8 @@ enum : int { M_PATH = RT_MODE_PATH, M_WHITTED = RT_MODE_WHITTED, M_PACKET = RT_M
 // each sample's value in F.samples; k_pt_finish then sums them in sample order.  Overlapped
 // primary+shadow frames (launch_render) store their samples the same way with one chunk.
 // ONE: every unit traces one sample (spp 1, or a sample split into single-sample chunks): no
-// sample loop and no running sum across the traversal
+// sample loop and no running sum across the traversal.  F must then be the record in place in the
+// kernel-argument segment (k_render_w8): the early accumulator read addresses it as constant memory.
 // DRY: the dry-run work frame (k_render_work) -- the same rays, nothing written (no accumulator,
 // frame, samples, ray counters or cycle costs)
 template <int MODE, int MAXD, bool TEX_SKY, class TR, bool WALKCHECK = false, bool ONE = false, bool DRY = false>
@@ -1362,6 +1425,7 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
                                             uint32_t unit, uint32_t lane) {
     // tile-major units: a workgroup's waves take the chunks of the same tiles (coherent rays,
     // shared cache lines); sample-major was 40 % slower on a 1/8 shard at spp 8
+    frame_phase(0);
     const uint32_t slot = F.nchunks <= 1 ? unit : unit / F.nchunks;
     const uint32_t entry = F.order ? F.order[slot] : slot;       // measured-cost dispatch order
     const uint32_t local_tile = entry & 0x0fffffffu;
@@ -1374,6 +1438,30 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
     const uint32_t x = (tile % F.tiles_x) * 8u + (lane & 7u), y = (tile / F.tiles_x) * 8u + (lane >> 3);
     const bool on = x < F.W && y < F.H && (!part_tile || (lane >> F.part_shift) == ((entry >> 28) & 7u));
     const uint32_t px = x + y * F.W;
+    // The single-sample build requests the pixel's accumulator here, before the rays, and consumes
+    // it in the epilogue: the frame's one long read (Infinity Cache or HBM) returns under the
+    // traversals instead of standing alone at the wave's end.  Only lanes that will write the pixel
+    // read it (on: inside the image and inside the entry's part), and only on frames that accumulate
+    // here (no reset, no stored samples).  Such a kernel runs on the caller's stream behind every
+    // earlier write of the accumulator (launch_render: frames on the renderer's streams store
+    // samples, and k_pt_finish accumulates them on the caller's stream).
+    // The three fields are read through an address the compiler cannot match with F's: merged with
+    // the epilogue's reads they would hold four scalar registers across both traversals, which the
+    // kernel does not have at 8 waves (4 v_writelane / 6 v_readlane).
+    constexpr bool kEarlyAcc = ONE && !DRY;
+    float4 acc_in = make_float4(0, 0, 0, 0);
+    if constexpr (kEarlyAcc) {
+        uintptr_t fa = (uintptr_t)&F;
+        asm volatile("" : "+s"(fa));
+        const auto *Fh = (const __attribute__((address_space(4))) FrameArgs *)fa;
+        const uint32_t reset = Fh->reset;
+        const float4 *const samples = Fh->samples, *const acc = Fh->acc;
+        if (on & (reset == 0u) & (samples == nullptr)) {
+            typedef float f32x4 __attribute__((ext_vector_type(4)));
+            const f32x4 v = *(const __attribute__((address_space(1))) f32x4 *)(uintptr_t)(acc + px);
+            acc_in = make_float4(v.x, v.y, v.z, v.w);
+        }
+    }
     // the wave-coherent camera-ray walk is compiled into the global-node primary+shadow
     // kernel only (SceneView::wave_primary picks it at run time)
     constexpr int kCamWave = (MODE == M_PATH && MAXD == 1 && TR::kStride == 256) ? (WALKCHECK ? 2 : 1) : 0;
@@ -1389,7 +1477,8 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
     } else if (ONE && on) {
         uint32_t seed = init_seed(px + F.W * F.H * (s_begin + F.spp * F.frame));
         DRay ray = primary_ray(F, x, y, seed);
-        sum = trace_path<MAXD, TEX_SKY, TR, kCamWave>(S, T, ray, (int)F.depth, seed, nshadow, nbounce);
+        frame_phase(1);
+        sum = trace_path<MAXD, TEX_SKY, TR, kCamWave, true>(S, T, ray, (int)F.depth, seed, nshadow, nbounce);
         if (F.samples) {
             F.samples[((size_t)s_begin * F.ntiles_local + local_tile) * 64u + lane] = make_float4(sum.x, sum.y, sum.z, 0.0f);
         }
@@ -1407,7 +1496,9 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
     if constexpr (DRY) return;
     if (on && !F.samples) {
         f3 res = (1.0f / (float)F.spp) * sum;
-        float4 a = F.reset ? make_float4(0, 0, 0, 0) : F.acc[px];
+        float4 a;
+        if constexpr (kEarlyAcc) a = acc_in;
+        else a = F.reset ? make_float4(0, 0, 0, 0) : F.acc[px];
         a.w += 1;                                                      // renderer.cpp:237-240
         const float w = a.w, inv = 1.0f / w;
         a = make_float4(a.x + inv * (res.x - a.x), a.y + inv * (res.y - a.y), a.z + inv * (res.z - a.z),
@@ -1422,6 +1513,7 @@ __device__ __forceinline__ void render_tile(const SceneView &S, const FrameArgs 
     }
     count_rays<MODE == M_PATH && MAXD == 1 && ONE>(F, unit, lane, nshadow, nbounce);
     if (F.tile_cost && lane == 0) F.tile_cost[local_tile] = (uint32_t)(__builtin_amdgcn_s_memtime() - t_start);
+    frame_phase(5);
 }
 
 // Global-node variant: 256-thread workgroups, wave w of workgroup b owns local tile b*4+w.
@@ -2532,3 +2624,16 @@ void launch_assemble(const uint32_t *gathered, uint32_t cap, uint32_t nshards, c
 #endif
 
 }  // namespace rt
+
+#if defined(RT_FRAME_PHASES) && !RT_EXT
+// diagnostic builds: the stamps of the core build's last frames (n <= kFramePhaseWaves * 8 words), and their reset
+extern "C" __attribute__((visibility("default"))) int rt_debug_frame_phases(unsigned long long *out, size_t n) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(rt::kcore::rt_frame_phase_buf), n * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
+}
+extern "C" __attribute__((visibility("default"))) int rt_debug_frame_phases_clear() {
+    void *p = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&p, HIP_SYMBOL(rt::kcore::rt_frame_phase_buf)) != hipSuccess) return -1;
+    return hipMemset(p, 0, sizeof(unsigned long long) * 8u * rt::kcore::kFramePhaseWaves) == hipSuccess ? 0 : -1;
+}
+#endif
