@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/rt_amd.h"
+#include "rt_variants.h"
 
 namespace rt {
 
@@ -91,16 +92,13 @@ struct FrameArgs {
                                         // ([2..5] the camera walk's counters, SceneView::walk_stats)
 };
 
-// One launch of the frame kernel family (Renderer::Tick): integrator mode, Trace depth
-// bucket, textured sky.
+// One launch of the frame kernel family (Renderer::Tick): which build (rt_variants.h), and where
+// (workgroups of 256 threads).
 struct FrameLaunch {
-    int mode;        // RT_MODE_*
-    int md;          // depth bucket: 1, 4, 10 or 32
-    bool tex;        // non-constant sky texture
-    dim3 grid, block;
+    FrameVariant v;
+    dim3 grid;
     size_t lds_bytes;
     hipStream_t stream;
-    int waves;       // primary+shadow frames: 8 = the single-sample build (k_render_w8), else the plain one
 };
 
 // Wavefront path tracing (RT_MODE_PATH, Trace depth >= 2): the frame's paths advance one
@@ -149,34 +147,30 @@ struct TraceArgs {
     uint32_t n, depth;
 };
 
-// Each kernel build provides the same launchers: `kcore` is compiled without the
-// extension primitives and materials (cubes, quads, quad light, TextureMaterial,
-// non-Light light materials), `kext` with them.  The host picks per scene.
-#define RT_DECLARE_LAUNCHERS(NS)                                                                  \
-    namespace NS {                                                                                \
-    void launch_frame(const SceneView &S, const FrameArgs &F, const FrameLaunch &L);              \
-    void launch_work(const SceneView &S, const FrameArgs &F, const FrameLaunch &L,               \
-                     uint32_t *tile_work, uint32_t *pixel_work);                                  \
-    void launch_intersect(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n,       \
-                          size_t lds, hipStream_t st);                                            \
-    void launch_occluded(const SceneView &S, const rt_ray *rays, uint8_t *out, uint32_t n,        \
-                         size_t lds, hipStream_t st);                                             \
-    void launch_intersect_packet(const SceneView &S, const rt_ray *rays, rt_hit *hits,            \
-                                 uint32_t n, hipStream_t st);                                     \
-    int launch_pt_level(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex,      \
-                        size_t lds, uint32_t num_cus, hipStream_t st);                            \
-    void launch_pt_lanes(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex,     \
-                         size_t lds, uint32_t num_cus, hipStream_t st);                           \
-    void launch_pt_finish(const FrameArgs &F, const PathArgs &P, bool last, hipStream_t st);      \
-    void launch_trace(const SceneView &S, const TraceArgs &A, int mode, int md, bool tex,         \
-                      size_t lds, hipStream_t st);                                                \
-    }
-RT_DECLARE_LAUNCHERS(kcore)
-RT_DECLARE_LAUNCHERS(kext)
-#undef RT_DECLARE_LAUNCHERS
+// Each kernel build provides the same launchers, one table each: `kcore` is compiled without
+// the extension primitives and materials (cubes, quads, quad light, TextureMaterial, non-Light
+// light materials), `kext` with them.  The host picks per scene (rt_device.hip: launchers(scene)).
+struct Launchers {
+    void (*frame)(const SceneView &S, const FrameArgs &F, const FrameLaunch &L);
+    void (*work)(const SceneView &S, const FrameArgs &F, const FrameLaunch &L, uint32_t *tile_work, uint32_t *pixel_work);
+    void (*intersect)(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, size_t lds, hipStream_t st);
+    void (*occluded)(const SceneView &S, const rt_ray *rays, uint8_t *out, uint32_t n, size_t lds, hipStream_t st);
+    void (*intersect_packet)(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, hipStream_t st);
+    // returns the lanes resident on the device
+    int (*pt_level)(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
+                    hipStream_t st);
+    void (*pt_lanes)(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
+                     hipStream_t st);
+    void (*pt_finish)(const FrameArgs &F, const PathArgs &P, bool last, hipStream_t st);
+    void (*trace)(const SceneView &S, const TraceArgs &A, const FrameVariant &v, size_t lds, hipStream_t st);
+};
+namespace kext {
+const Launchers &launchers();
+}
 // BVH analysis (RT_MODE_BVH_HEAT frames, rt_bvh_visualize): node reads only, so the core build
 // carries it for every scene.  launch_heat: F.depth = the tree's depth, plain tile order.
 namespace kcore {
+const Launchers &launchers();
 void launch_heat(const SceneView &S, const FrameArgs &F, size_t lds, hipStream_t st);
 void launch_visualize(const SceneView &S, const rt_ray *rays, uint32_t *counts, uint32_t n, size_t lds, hipStream_t st);
 }

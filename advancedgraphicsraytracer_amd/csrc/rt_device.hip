@@ -347,8 +347,8 @@ size_t stack_bytes(const rt_scene *s) { return (size_t)s->stack_depth * 256u * s
 size_t walk_bytes(const rt_scene *s, const SceneView &v) {
     return v.wave_primary ? (size_t)s->stack_depth * 4u * sizeof(uint32_t) : 0u;
 }
-// the compiled MAXD class a Trace depth runs in
-int max_depth_class(uint32_t depth) { return depth <= 1 ? 1 : depth <= 4 ? 4 : depth <= 10 ? 10 : 32; }
+// the scene's kernel family: the extension build where the scene holds what only it knows
+const Launchers &launchers(const rt_scene *s) { return s->ext ? kext::launchers() : kcore::launchers(); }
 // pixels covered by a frame / shard launch (primary rays per sample)
 uint64_t frame_pixels(const rt_renderer *r, const FrameArgs &F, uint32_t shard, uint32_t nshards, uint32_t tiles_x,
                       uint32_t ntiles) {
@@ -551,6 +551,7 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
     }
     bool used[kPtMaxSlots] = {};
     const size_t lds = stack_bytes(s);
+    const Launchers &K = launchers(s);
     // levels are compacted level by level until one is small enough to drain (k_pt_level)
     const uint32_t drain_level = s->pt_drain_level;
     for (uint32_t s0 = 0; s0 < F.spp; s0 += (uint32_t)batch) {
@@ -600,12 +601,10 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
             P.queue_out = (level & 1u) ? q0 : q1;
             int resident = 0;
             if (level > 0 && s->pt_lanes) {             // incoherent levels: the lane state machine
-                if (s->ext) kext::launch_pt_lanes(view, F, P, tex, lds, s->num_cus, X);
-                else kcore::launch_pt_lanes(view, F, P, tex, lds, s->num_cus, X);
+                K.pt_lanes(view, F, P, tex, lds, s->num_cus, X);
             } else {
                 const size_t lv = level == 0 ? lds + walk_bytes(s, view) : lds;   // camera rays: the walk's words
-                resident = s->ext ? kext::launch_pt_level(view, F, P, tex, lv, s->num_cus, X)
-                                  : kcore::launch_pt_level(view, F, P, tex, lv, s->num_cus, X);
+                resident = K.pt_level(view, F, P, tex, lv, s->num_cus, X);
             }
             if (level >= dlevel) break;                // that launch finished every remaining level
             if (level == 0) {
@@ -616,8 +615,7 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
         }
         if (!pipe) {   // serial: this batch's samples onto the running sum (the last: accumulate, RGB8)
             const bool last = s0 + P.batch_spp >= F.spp;
-            if (s->ext) kext::launch_pt_finish(F, P, last, st);
-            else kcore::launch_pt_finish(F, P, last, st);
+            K.pt_finish(F, P, last, st);
         }
     }
     if (pipe) {
@@ -633,8 +631,7 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
         P.sum = r->d_sum;
         P.s0 = 0;
         P.batch_spp = F.spp;
-        if (s->ext) kext::launch_pt_finish(F, P, true, st);
-        else kcore::launch_pt_finish(F, P, true, st);
+        K.pt_finish(F, P, true, st);
         HIP_TRY(hipEventRecord(r->pt_fin[par], st));
         r->pt_fin_set[par] = true;
     }
@@ -710,23 +707,6 @@ std::vector<uint32_t> xcd_grouped_order(const FrameArgs &F, const uint32_t *map,
         }
     }
     return out;
-}
-
-// The primary+shadow frame kernel's build (FrameLaunch::waves): frames of one sample per work
-// unit run k_render_w8 (render_tile ONE: no sample loop, 51 VGPRs, 8 waves/SIMD where the LDS
-// stacks allow), others the plain k_render (71 VGPRs, 7 waves).
-void frame_build(const rt_renderer *r, const SceneView &view, const FrameArgs &F, FrameLaunch &L, bool overlapped) {
-    const rt_scene *s = r->scene;
-    L.waves = 7;
-    if (L.mode != RT_MODE_PATH || L.md != 1 || s->frame_waves == 7) return;
-    if (F.nchunks != std::max(1u, F.spp)) return;   // the single-sample build: one sample per unit
-    if (view.wave_primary && view.walk_check != RT_WALK_CHECK_OFF) return;   // the walk-check build
-    // small overlapped frames (<= 3 rounds of resident waves: TEAPOT-F 720p with 4 in flight
-    // 0.059 -> 0.062 ms) keep the plain build; everywhere else the single-sample build won or
-    // tied (TEAPOT-F 1080p serial 0.1025 -> 0.096, 2 in flight 0.108 -> 0.099; mig29 x16 1080p 4 in
-    // flight 0.223 -> 0.215, serial 0.466 -> 0.471; profiles/r04/frame_build/one_*.log)
-    if (overlapped && F.nunits <= 3u * 4u * 5u * s->num_cus && s->frame_waves != 8) return;
-    L.waves = 8;
 }
 
 // The tile costs and the order of parameter set `key` with n local tiles: a new set drops what the
@@ -959,10 +939,8 @@ int work_frame(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
     view.wave_primary = 0;
     view.walk_check = RT_WALK_CHECK_OFF;
     view.walk_stats = nullptr;
-    const int md = p->depth <= 1 ? 1 : 32;
-    FrameLaunch L{RT_MODE_PATH, md, !s->view.sky_const, dim3((n + 3) / 4), dim3(256), stack_bytes(s), st, 0};
-    if (s->ext) kext::launch_work(view, F, L, r->d_work, pixel_work);
-    else kcore::launch_work(view, F, L, r->d_work, pixel_work);
+    const FrameLaunch L{work_variant(p->depth, !s->view.sky_const), dim3((n + 3) / 4), stack_bytes(s), st};
+    launchers(s).work(view, F, L, r->d_work, pixel_work);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(work.data(), r->d_work, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1155,8 +1133,7 @@ int submit_frame(rt_renderer *r, const SceneView &view, const FrameArgs &F, cons
     const rt_scene *s = r->scene;
     if (o.walk.ev_before >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kWalk][o.walk.ev_before], st));
     if (o.split.ev_before >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kSplit][o.split.ev_before], st));
-    if (s->ext) kext::launch_frame(view, F, L);
-    else kcore::launch_frame(view, F, L);
+    launchers(s).frame(view, F, L);
     HIP_TRY(hipGetLastError());
     if (o.walk.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kWalk][o.walk.ev_after], st));
     if (o.split.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kSplit][o.split.ev_after], st));
@@ -1168,8 +1145,7 @@ int submit_frame(rt_renderer *r, const SceneView &view, const FrameArgs &F, cons
         PathArgs P{};
         P.batch_spp = F.spp;
         P.result = F.samples;
-        if (s->ext) kext::launch_pt_finish(F, P, true, st);
-        else kcore::launch_pt_finish(F, P, true, st);
+        launchers(s).pt_finish(F, P, true, st);
         HIP_TRY(hipGetLastError());
         if (o.depth > 0) {
             HIP_TRY(hipEventRecord(r->ps_fin[o.buf], st));
@@ -1228,8 +1204,6 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
         return RT_OK;
     }
     if (p->depth > 32) return fail(RT_ERR_UNSUPPORTED, "Trace depth above 32");   // = kWHITTED_MAX
-    const int md = max_depth_class(p->depth);
-    const bool tex = !s->view.sky_const;
     const int mode = (int)p->mode;
     const bool wavefront = mode == RT_MODE_PATH && p->depth >= 2 && s->pt_wavefront;
     if (int rc = sample_split(r, p->spp, mode != RT_MODE_PACKET && !wavefront, F); rc != RT_OK) return rc;
@@ -1239,7 +1213,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
         r->frames += 1;
         return RT_OK;
     }
-    FrameLaunch L{mode, md, tex, dim3((F.nunits + 3) / 4), dim3(256), stack_bytes(s), st, s->frame_waves};
+    FrameLaunch L{{}, dim3((F.nunits + 3) / 4), stack_bytes(s), st};
     SceneView view = s->view;
     view.walk_stats = r->d_counters;
     view.walk_check = r->walk_check;
@@ -1249,7 +1223,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     // did the GPU run dry since the previous frame?  (a timed group then restarts: kTuneRestarts)
     P.stalled = r->stall_armed && hipEventQuery(r->stall_ev) == hipSuccess;
     r->stall_armed = false;
-    const bool ps_kernel = mode == RT_MODE_PATH && md == 1;   // the primary+shadow frame kernel
+    const bool ps_kernel = primary_shadow(mode, p->depth);   // the primary+shadow frame kernel
     if (int rc = walk_step(r, ps_kernel && !s->ext, view, P); rc != RT_OK) return rc;
     if (s->tile_order) {
         // half-tile units: primary+shadow frames of the global-node kernel, whole-tile units only
@@ -1265,10 +1239,25 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     if (L.stream != st)
         if (int rc = after_updates(s, L.stream); rc != RT_OK) return rc;
     L.lds_bytes = stack_bytes(s) + walk_bytes(s, view);   // the camera walk's word stack when it runs
-    frame_build(r, view, F, L, P.depth > 0);
+    L.v = frame_variant({mode, p->depth, !view.sky_const, s->frame_waves, F.nchunks, F.spp, F.nunits, s->num_cus,
+                         P.depth > 0, view.wave_primary, view.walk_check});
     if (int rc = submit_frame(r, view, F, L, P, st); rc != RT_OK) return rc;
     r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
     r->frames += 1;
+    return RT_OK;
+}
+
+// rt_intersect / rt_occluded / rt_intersect_packets / rt_bvh_visualize: one batch of the caller's
+// device rays, after the scene's pending updates, on the caller's stream
+template <class Launch>
+int ray_call(rt_scene *s, const void *rays, void *out, uint32_t n, void *stream, const char *null_text, Launch launch) {
+    if (!s || (n && (!rays || !out))) return fail(RT_ERR_INVALID, null_text);
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
+    launch(st);
+    HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
@@ -1452,39 +1441,18 @@ int rt_scene_copy_bvh(const rt_scene *cs, void *nodes, uint32_t *indices) {
 }
 
 int rt_intersect(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {
-    if (!s || (n && (!rays || !hits))) return fail(RT_ERR_INVALID, "rt_intersect: null argument");
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
-    if (s->ext) kext::launch_intersect(s->view, rays, hits, n, stack_bytes(s), st);
-    else kcore::launch_intersect(s->view, rays, hits, n, stack_bytes(s), st);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return ray_call(s, rays, hits, n, stream, "rt_intersect: null argument",
+                    [&](hipStream_t st) { launchers(s).intersect(s->view, rays, hits, n, stack_bytes(s), st); });
 }
 
 int rt_occluded(rt_scene *s, const rt_ray *rays, uint8_t *out, uint32_t n, void *stream) {
-    if (!s || (n && (!rays || !out))) return fail(RT_ERR_INVALID, "rt_occluded: null argument");
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
-    if (s->ext) kext::launch_occluded(s->view, rays, out, n, stack_bytes(s), st);
-    else kcore::launch_occluded(s->view, rays, out, n, stack_bytes(s), st);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return ray_call(s, rays, out, n, stream, "rt_occluded: null argument",
+                    [&](hipStream_t st) { launchers(s).occluded(s->view, rays, out, n, stack_bytes(s), st); });
 }
 
 int rt_intersect_packets(rt_scene *s, const rt_ray *rays, rt_hit *hits, uint32_t n, void *stream) {
-    if (!s || (n && (!rays || !hits))) return fail(RT_ERR_INVALID, "rt_intersect_packets: null argument");
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
-    if (s->ext) kext::launch_intersect_packet(s->view, rays, hits, n, st);
-    else kcore::launch_intersect_packet(s->view, rays, hits, n, st);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return ray_call(s, rays, hits, n, stream, "rt_intersect_packets: null argument",
+                    [&](hipStream_t st) { launchers(s).intersect_packet(s->view, rays, hits, n, st); });
 }
 int rt_trace(rt_scene *s, int mode, const rt_ray *rays, uint32_t *seeds, const uint8_t *flags, uint32_t depth,
              float *radiance, rt_hit *hits, uint64_t *ray_counts, uint32_t n, void *stream) {
@@ -1497,11 +1465,9 @@ int rt_trace(rt_scene *s, int mode, const rt_ray *rays, uint32_t *seeds, const u
     A.rays = rays; A.seeds = seeds; A.flags = flags; A.radiance = radiance; A.hits = hits;
     A.counts = reinterpret_cast<unsigned long long *>(ray_counts);
     A.n = n; A.depth = depth;
-    const bool tex = !s->view.sky_const;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = after_updates(s, st); rc != RT_OK) return rc;
-    if (s->ext) kext::launch_trace(s->view, A, mode, max_depth_class(depth), tex, stack_bytes(s), st);
-    else kcore::launch_trace(s->view, A, mode, max_depth_class(depth), tex, stack_bytes(s), st);
+    launchers(s).trace(s->view, A, trace_variant(mode, depth, !s->view.sky_const), stack_bytes(s), st);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -1566,13 +1532,8 @@ int rt_intersect_packets_host(rt_scene *s, const rt_ray *rays, rt_hit *hits, uin
 
 // Batched Scene::BVHVisualization (k_bvh_visualize; the core build serves every scene: nodes only)
 int rt_bvh_visualize(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t n, void *stream) {
-    if (!s || (n && (!rays || !counts))) return fail(RT_ERR_INVALID, "rt_bvh_visualize: null argument");
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(s->device));
-    if (int rc = after_updates(s, (hipStream_t)stream); rc != RT_OK) return rc;
-    kcore::launch_visualize(s->view, rays, counts, n, stack_bytes(s), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return ray_call(s, rays, counts, n, stream, "rt_bvh_visualize: null argument",
+                    [&](hipStream_t st) { kcore::launch_visualize(s->view, rays, counts, n, stack_bytes(s), st); });
 }
 int rt_bvh_visualize_host(rt_scene *s, const rt_ray *rays, uint32_t *counts, uint32_t n) {
     return staged_call(s, rays, counts, 2 * sizeof(uint32_t), n, CALL_VISUALIZE);
@@ -1872,13 +1833,8 @@ const char *rt_frame_kernel_name(const rt_renderer *r, const rt_frame_params *p)
     }
     const rt_scene *s = r->scene;
     if (p->mode == RT_MODE_PATH && p->depth >= 2 && s->pt_wavefront) return "k_pt_level";
-    const int md = max_depth_class(p->depth);
-    static const char *names[3][4] = {
-        {"k_render<path,1>", "k_render<path,4>", "k_render<path,10>", "k_render<path,32>"},
-        {"k_render<whitted,1>", "k_render<whitted,1>", "k_render<whitted,1>", "k_render<whitted,1>"},
-        {"k_render<packet,1>", "k_render<packet,10>", "k_render<packet,10>", "k_render<packet,32>"}};
-    const int col = md == 1 ? 0 : md == 4 ? 1 : md == 10 ? 2 : 3;
-    return names[p->mode][col];
+    // the class launch_render's frame_variant starts from; the name does not depend on the build
+    return frame_variant_name(kernel_class((int)p->mode, p->depth, !s->view.sky_const));
 }
 
 int rt_renderer_stream(rt_renderer *r, void **stream) {

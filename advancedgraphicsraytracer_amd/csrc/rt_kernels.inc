@@ -1532,7 +1532,7 @@ __global__ __launch_bounds__(256, RT_RENDER_WAVES_PER_SIMD) void k_render(SceneV
 // The primary+shadow frame for work units of one sample (spp 1, or a sample split into single-
 // sample chunks): render_tile without the sample loop and its running sum, which the plain build
 // carries across the traversal -- 51 VGPRs instead of 71, no spill, so 8 waves/SIMD where the LDS
-// stacks allow (TEAPOT-F 1080p serial 0.1025 -> 0.096 ms).  Round 4; frame_build picks it.
+// stacks allow (TEAPOT-F 1080p serial 0.1025 -> 0.096 ms).  Round 4; frame_variant picks it.
 // The two argument records (about 110 dwords) are read where they are used, from the kernel-
 // argument segment: named as parameters they are all loaded at entry, more scalars than the
 // kernel has registers for, and the compiler parked them in the lanes of a VGPR (42 v_writelane /
@@ -2439,52 +2439,68 @@ __global__ __launch_bounds__(256) void k_pt_finish(FrameArgs F, PathArgs P, int 
 }
 
 // ------------------------------------------------------------------ launchers
-void launch_work(const SceneView &S, const FrameArgs &F, const FrameLaunch &L, uint32_t *tile_work, uint32_t *pixel_work) {
+// Each family's (variant -> kernel) pairing is written once, as a lookup of the kernel's host
+// address: launch_kernel starts it, resident_blocks asks its occupancy.  The P... are the kernel's
+// parameter types, which the builds of one family share.
+template <class... P>
+static void launch_kernel(const void *fn, dim3 grid, size_t lds, hipStream_t st, const P &...args) {
+    void *argv[] = {const_cast<void *>(static_cast<const void *>(&args))...};
+    (void)hipLaunchKernel(fn, grid, dim3(256), argv, lds, st);   // (an error stays for the caller's hipGetLastError)
+}
+#define RT_SKY(TEX, K) ((TEX) ? (const void *)K<true> : (const void *)K<false>)
+#define RT_SKY_OF(TEX, K, ...) ((TEX) ? (const void *)K<__VA_ARGS__, true> : (const void *)K<__VA_ARGS__, false>)
+// k_render / k_render_w8 / k_render_walkcheck (SceneView, FrameArgs)
+static const void *frame_kernel(const FrameVariant &v) {
+    if (v.build == FrameBuild::WalkCheck) return RT_SKY(v.tex, k_render_walkcheck);
+    if (v.build == FrameBuild::SingleSample) return RT_SKY(v.tex, k_render_w8);
+    switch (v.mode * 64 + v.maxd) {   // depth = the bounces' Trace depth (PACKET: 0 allowed)
+    case M_PATH * 64 + 1: return RT_SKY_OF(v.tex, k_render, M_PATH, 1);
+    case M_PATH * 64 + 4: return RT_SKY_OF(v.tex, k_render, M_PATH, 4);
+    case M_PATH * 64 + 10: return RT_SKY_OF(v.tex, k_render, M_PATH, 10);
+    case M_PATH * 64 + 32: return RT_SKY_OF(v.tex, k_render, M_PATH, 32);
+    case M_WHITTED * 64 + 1: return RT_SKY_OF(v.tex, k_render, M_WHITTED, 1);
+    case M_PACKET * 64 + 1: return RT_SKY_OF(v.tex, k_render, M_PACKET, 1);
+    case M_PACKET * 64 + 10: return RT_SKY_OF(v.tex, k_render, M_PACKET, 10);
+    case M_PACKET * 64 + 32: return RT_SKY_OF(v.tex, k_render, M_PACKET, 32);
+    }
+    return nullptr;   // no such build (rt_variants.h computes none): the launch fails
+}
+// k_render_work (SceneView, FrameArgs, tile work, pixel work, with distances)
+static const void *work_kernel(const FrameVariant &v) {
+    return v.maxd == 1 ? RT_SKY_OF(v.tex, k_render_work, 1) : RT_SKY_OF(v.tex, k_render_work, 32);
+}
+// k_trace (SceneView, TraceArgs)
+static const void *trace_kernel(const FrameVariant &v) {
+    switch (v.mode * 64 + v.maxd) {
+    case M_PATH * 64 + 1: return RT_SKY_OF(v.tex, k_trace, M_PATH, 1);
+    case M_PATH * 64 + 4: return RT_SKY_OF(v.tex, k_trace, M_PATH, 4);
+    case M_PATH * 64 + 10: return RT_SKY_OF(v.tex, k_trace, M_PATH, 10);
+    case M_PATH * 64 + 32: return RT_SKY_OF(v.tex, k_trace, M_PATH, 32);
+    case M_WHITTED * 64 + 1: return RT_SKY_OF(v.tex, k_trace, M_WHITTED, 1);
+    }
+    return nullptr;
+}
+// k_pt_level0 (camera rays: the level-0-only build) / k_pt_level, k_pt_lanes (SceneView, FrameArgs, PathArgs)
+static const void *pt_level_kernel(bool level0, bool tex) {
+    return level0 ? RT_SKY(tex, k_pt_level0) : RT_SKY(tex, k_pt_level);
+}
+static const void *pt_lanes_kernel(bool quad, bool tex) {
+    return quad ? (tex ? (const void *)k_pt_lanes<true, true> : (const void *)k_pt_lanes<false, true>)
+                : (tex ? (const void *)k_pt_lanes<true, false> : (const void *)k_pt_lanes<false, false>);
+}
+#undef RT_SKY
+#undef RT_SKY_OF
+
+static void launch_work(const SceneView &S, const FrameArgs &F, const FrameLaunch &L, uint32_t *tile_work, uint32_t *pixel_work) {
     // stack, entry distances (counters [4] / [5], left out past 64 KB: trees deeper than 28), counters
     const size_t cnt = kWorkCounterBytes;
     const int wd = 2u * L.lds_bytes + cnt <= kLdsLaunchMax ? 1 : 0;
     const size_t lds = (wd ? 2u : 1u) * L.lds_bytes + cnt;
-    if (L.md == 1) {
-        if (L.tex) hipLaunchKernelGGL((k_render_work<1, true>), L.grid, L.block, lds, L.stream, S, F, tile_work, pixel_work, wd);
-        else hipLaunchKernelGGL((k_render_work<1, false>), L.grid, L.block, lds, L.stream, S, F, tile_work, pixel_work, wd);
-    } else {
-        if (L.tex) hipLaunchKernelGGL((k_render_work<32, true>), L.grid, L.block, lds, L.stream, S, F, tile_work, pixel_work, wd);
-        else hipLaunchKernelGGL((k_render_work<32, false>), L.grid, L.block, lds, L.stream, S, F, tile_work, pixel_work, wd);
-    }
+    launch_kernel<SceneView, FrameArgs, uint32_t *, uint32_t *, int>(work_kernel(L.v), L.grid, lds, L.stream, S, F, tile_work,
+                                                                     pixel_work, wd);
 }
-
-void launch_frame(const SceneView &S, const FrameArgs &F, const FrameLaunch &L) {
-#define RT_LAUNCH(MO, MD, TX) hipLaunchKernelGGL((k_render<MO, MD, TX>), L.grid, L.block, L.lds_bytes, L.stream, S, F)
-    if (L.mode == RT_MODE_PATH && L.md == 1 && S.wave_primary && S.walk_check != RT_WALK_CHECK_OFF) {
-        if (L.tex) hipLaunchKernelGGL(k_render_walkcheck<true>, L.grid, L.block, L.lds_bytes, L.stream, S, F);
-        else hipLaunchKernelGGL(k_render_walkcheck<false>, L.grid, L.block, L.lds_bytes, L.stream, S, F);
-    } else if (L.mode == RT_MODE_PATH && L.md == 1 && L.waves == 8) {
-        if (L.tex) hipLaunchKernelGGL(k_render_w8<true>, L.grid, L.block, L.lds_bytes, L.stream, S, F);
-        else hipLaunchKernelGGL(k_render_w8<false>, L.grid, L.block, L.lds_bytes, L.stream, S, F);
-    } else if (L.mode == RT_MODE_WHITTED) {
-        if (L.tex) RT_LAUNCH(M_WHITTED, 1, true); else RT_LAUNCH(M_WHITTED, 1, false);
-    } else if (L.mode == RT_MODE_PACKET) {   // depth = the bounces' Trace depth (0 allowed)
-        switch (L.md * 2 + (L.tex ? 1 : 0)) {
-        case 2: RT_LAUNCH(M_PACKET, 1, false); break;
-        case 3: RT_LAUNCH(M_PACKET, 1, true); break;
-        case 8: case 20: RT_LAUNCH(M_PACKET, 10, false); break;
-        case 9: case 21: RT_LAUNCH(M_PACKET, 10, true); break;
-        case 64: RT_LAUNCH(M_PACKET, 32, false); break;
-        default: RT_LAUNCH(M_PACKET, 32, true); break;
-        }
-    } else {
-        switch (L.md * 2 + (L.tex ? 1 : 0)) {
-        case 2: RT_LAUNCH(M_PATH, 1, false); break;
-        case 3: RT_LAUNCH(M_PATH, 1, true); break;
-        case 8: RT_LAUNCH(M_PATH, 4, false); break;
-        case 9: RT_LAUNCH(M_PATH, 4, true); break;
-        case 20: RT_LAUNCH(M_PATH, 10, false); break;
-        case 21: RT_LAUNCH(M_PATH, 10, true); break;
-        case 64: RT_LAUNCH(M_PATH, 32, false); break;
-        default: RT_LAUNCH(M_PATH, 32, true); break;
-        }
-    }
-#undef RT_LAUNCH
+static void launch_frame(const SceneView &S, const FrameArgs &F, const FrameLaunch &L) {
+    launch_kernel<SceneView, FrameArgs>(frame_kernel(L.v), L.grid, L.lds_bytes, L.stream, S, F);
 }
 // workgroups of 256 threads of kernel fn resident per CU with lds bytes of dynamic LDS, on the
 // current device; cached per (device, kernel, lds bytes): scenes with deeper trees need more
@@ -2505,70 +2521,44 @@ static int resident_blocks(const void *fn, size_t lds) {
 }
 // one bounce level of the wavefront path tracer: as many workgroups as stay resident
 // (the level's queue is walked wave-strided, so every wave gets an equal share)
-int launch_pt_level(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
-                    hipStream_t st) {
-    const int pc = resident_blocks(tex ? (const void *)k_pt_level<true> : (const void *)k_pt_level<false>, lds);
+static int launch_pt_level(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
+                           hipStream_t st) {
+    const int pc = resident_blocks(pt_level_kernel(false, tex), lds);
     // level 0 (every path, costs vary by tile): one wave per 64 paths, balanced by the
     // hardware dispatcher; deeper levels: as many workgroups as stay resident walk the
     // queue wave-strided (a full grid of mostly empty workgroups measured 9-14 % slower)
     const uint32_t need = (P.npaths + 255u) / 256u;
     const uint32_t grid = P.level == 0 ? need : std::min(need, (uint32_t)pc * num_cus);
-    if (P.level == 0) {   // camera rays: the level-0-only build (k_pt_level0)
-        if (tex) hipLaunchKernelGGL(k_pt_level0<true>, dim3(grid), dim3(256), lds, st, S, F, P);
-        else hipLaunchKernelGGL(k_pt_level0<false>, dim3(grid), dim3(256), lds, st, S, F, P);
-    } else if (tex) {
-        hipLaunchKernelGGL(k_pt_level<true>, dim3(grid), dim3(256), lds, st, S, F, P);
-    } else {
-        hipLaunchKernelGGL(k_pt_level<false>, dim3(grid), dim3(256), lds, st, S, F, P);
-    }
+    launch_kernel<SceneView, FrameArgs, PathArgs>(pt_level_kernel(P.level == 0, tex), dim3(grid), lds, st, S, F, P);
     return pc * (int)num_cus * 256;   // resident lanes
 }
 // the lane state-machine kernel for a level (resident grid)
-void launch_pt_lanes(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
-                     hipStream_t st) {
-    const bool quad = S.quad_lanes && S.quads;
-    const void *fn = quad ? (tex ? (const void *)k_pt_lanes<true, true> : (const void *)k_pt_lanes<false, true>)
-                          : (tex ? (const void *)k_pt_lanes<true, false> : (const void *)k_pt_lanes<false, false>);
-    const int pc = resident_blocks(fn, lds);
-    const uint32_t grid = std::min((P.npaths + 255u) / 256u, (uint32_t)pc * num_cus);
-    if (quad) {
-        if (tex) hipLaunchKernelGGL((k_pt_lanes<true, true>), dim3(grid), dim3(256), lds, st, S, F, P);
-        else hipLaunchKernelGGL((k_pt_lanes<false, true>), dim3(grid), dim3(256), lds, st, S, F, P);
-    } else {
-        if (tex) hipLaunchKernelGGL((k_pt_lanes<true, false>), dim3(grid), dim3(256), lds, st, S, F, P);
-        else hipLaunchKernelGGL((k_pt_lanes<false, false>), dim3(grid), dim3(256), lds, st, S, F, P);
-    }
+static void launch_pt_lanes(const SceneView &S, const FrameArgs &F, const PathArgs &P, bool tex, size_t lds, uint32_t num_cus,
+                            hipStream_t st) {
+    const void *fn = pt_lanes_kernel(S.quad_lanes && S.quads, tex);
+    const uint32_t grid = std::min((P.npaths + 255u) / 256u, (uint32_t)resident_blocks(fn, lds) * num_cus);
+    launch_kernel<SceneView, FrameArgs, PathArgs>(fn, dim3(grid), lds, st, S, F, P);
 }
-void launch_pt_finish(const FrameArgs &F, const PathArgs &P, bool last, hipStream_t st) {
+static void launch_pt_finish(const FrameArgs &F, const PathArgs &P, bool last, hipStream_t st) {
     hipLaunchKernelGGL(k_pt_finish, dim3((F.ntiles_local * 64u + 255u) / 256u), dim3(256), 0, st, F, P, last ? 1 : 0);
 }
-void launch_trace(const SceneView &S, const TraceArgs &A, int mode, int md, bool tex, size_t lds, hipStream_t st) {
-    const dim3 grid((A.n + 255u) / 256u), block(256);
-#define RT_TRACE(M, D, X) hipLaunchKernelGGL((k_trace<M, D, X>), grid, block, lds, st, S, A)
-    if (mode == RT_MODE_WHITTED) {
-        if (tex) RT_TRACE(M_WHITTED, 1, true); else RT_TRACE(M_WHITTED, 1, false);
-        return;
-    }
-    switch (md * 2 + (tex ? 1 : 0)) {
-    case 2: RT_TRACE(M_PATH, 1, false); break;
-    case 3: RT_TRACE(M_PATH, 1, true); break;
-    case 8: RT_TRACE(M_PATH, 4, false); break;
-    case 9: RT_TRACE(M_PATH, 4, true); break;
-    case 20: RT_TRACE(M_PATH, 10, false); break;
-    case 21: RT_TRACE(M_PATH, 10, true); break;
-    case 64: RT_TRACE(M_PATH, 32, false); break;
-    default: RT_TRACE(M_PATH, 32, true); break;
-    }
-#undef RT_TRACE
+static void launch_trace(const SceneView &S, const TraceArgs &A, const FrameVariant &v, size_t lds, hipStream_t st) {
+    launch_kernel<SceneView, TraceArgs>(trace_kernel(v), dim3((A.n + 255u) / 256u), lds, st, S, A);
 }
-void launch_intersect(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, size_t lds, hipStream_t st) {
+static void launch_intersect(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, size_t lds, hipStream_t st) {
     hipLaunchKernelGGL(k_intersect, dim3((n + 255) / 256), dim3(256), lds, st, S, rays, hits, n);
 }
-void launch_occluded(const SceneView &S, const rt_ray *rays, uint8_t *out, uint32_t n, size_t lds, hipStream_t st) {
+static void launch_occluded(const SceneView &S, const rt_ray *rays, uint8_t *out, uint32_t n, size_t lds, hipStream_t st) {
     hipLaunchKernelGGL(k_occluded, dim3((n + 255) / 256), dim3(256), lds, st, S, rays, out, n);
 }
-void launch_intersect_packet(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, hipStream_t st) {
+static void launch_intersect_packet(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_intersect_packet, dim3((n + 255) / 256), dim3(256), 0, st, S, rays, hits, n);
+}
+// (a function's static, not a namespace-scope constant: the device pass would emit that one too)
+const Launchers &launchers() {
+    static const Launchers table = {launch_frame,    launch_work,     launch_intersect, launch_occluded, launch_intersect_packet,
+                                    launch_pt_level, launch_pt_lanes, launch_pt_finish, launch_trace};
+    return table;
 }
 #if RT_EXT == 0
 void launch_heat(const SceneView &S, const FrameArgs &F, size_t lds, hipStream_t st) {

@@ -14,7 +14,7 @@ struct rt_scene {
     uint32_t num_prims = 0;
     uint32_t num_materials = 0; // what an inserted triangle's material index is checked against
     uint32_t stack_depth = 0;   // LDS stack entries per lane
-    int frame_waves = 0;        // primary+shadow frame kernel build (frame_build): 0 = chosen, 7 = the
+    int frame_waves = 0;        // primary+shadow frame kernel build (frame_variant): 0 = chosen, 7 = the
                                 // plain build, 8 = the single-sample one wherever it applies (RT_FRAME_WAVES)
     uint32_t num_cus = 256;     // CUs of the device (resident grids, frames-in-flight rules)
     bool has_cubes = false;     // cube acceptance depends on the visiting order: no wave walk
