@@ -11,6 +11,7 @@ Everything computes on the GPU through librtamd.so; there is no CPU fallback.  A
 missing library or device raises RTError.  Device buffers are torch tensors (torch is
 plumbing here: memory, streams, torch.distributed).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -123,6 +124,15 @@ class Counters(C.Structure):
 
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("tmax", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("obj", "<i4"), ("u", "<f4"), ("v", "<f4")])
+GNORMAL_DTYPE = np.dtype([("n", "<f4", 3), ("material", "<i4")])   # rt_gnormal
+GALBEDO_DTYPE = np.dtype([("rgb", "<f4", 3), ("kind", "<i4")])     # rt_galbedo
+GBUFFER_PLANES = ("ray", "hit", "normal", "albedo")                  # rt_gbuffer's fields, in order
+_GBUFFER_DTYPES = {"ray": RAY_DTYPE, "hit": HIT_DTYPE, "normal": GNORMAL_DTYPE, "albedo": GALBEDO_DTYPE}
+
+
+class GBuffer(C.Structure):
+    """rt_gbuffer: one optional plane pointer each (device or host memory, by the entry point)"""
+    _fields_ = [(n, C.c_void_p) for n in GBUFFER_PLANES]
 
 _lib = None
 
@@ -222,6 +232,13 @@ def lib():
         "rt_renderer_destroy": ([vp], C.c_int),
         "rt_render_frame": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), vp, vp], C.c_int),
         "rt_render_frame_host": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), vp], C.c_int),
+        "rt_render_gbuffer": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), u32, u32, u32, u32, u32, C.POINTER(GBuffer), vp],
+                              C.c_int),
+        "rt_render_gbuffer_host": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), u32, u32, u32, u32, u32, C.POINTER(GBuffer)],
+                                   C.c_int),
+        "rt_gbuffer_pixels": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), u32, vp, u32, C.POINTER(GBuffer), vp], C.c_int),
+        "rt_gbuffer_pixels_host": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), u32, vp, u32, C.POINTER(GBuffer)], C.c_int),
+        "rt_renderer_gbuffer_walk": ([vp, C.c_int, C.POINTER(C.c_int), C.POINTER(u32)], C.c_int),
         "rt_shard_capacity": ([u32, u32, u32, C.POINTER(u32)], C.c_int),
         "rt_render_shard": ([vp, C.POINTER(Camera), C.POINTER(FrameParams), u32, u32, vp, vp], C.c_int),
         "rt_assemble_shards": ([vp, vp, u32, vp, vp], C.c_int),
@@ -1142,6 +1159,120 @@ class Renderer:
         if frame is None:
             self.frame += 1
         return out
+
+    # ---- first-hit G-buffer and picking (rt_render_gbuffer, rt_gbuffer_pixels): queries -- no frame,
+    # accumulator, counter or timed choice changes, and self.frame does not advance
+    def _gbuffer_params(self, planes, sample, spp, frame):
+        planes = tuple(planes)
+        if not planes or any(n not in GBUFFER_PLANES for n in planes) or len(set(planes)) != len(planes):
+            raise RTError(RT_ERR_INVALID, f"planes must be distinct names out of {GBUFFER_PLANES}")
+        return planes, FrameParams(self.width, self.height, spp, 1, self.frame if frame is None else frame, MODE_PATH, 0)
+
+    def _gbuffer_rect(self, rect):
+        x0, y0, w, h = (0, 0, self.width, self.height) if rect is None else (int(v) for v in rect)
+        if w <= 0 or h <= 0:   # (refused here: an empty plane has no address for the library to refuse it with)
+            raise RTError(RT_ERR_INVALID, "gbuffer: empty rectangle")
+        if x0 < 0 or y0 < 0:
+            raise RTError(RT_ERR_INVALID, "gbuffer: the rectangle leaves the frame")
+        return x0, y0, w, h
+
+    def _pixel_list(self, pixels):
+        """Pixel indices x + y*W; an [n, 2] array holds (x, y) pairs."""
+        a = np.asarray(pixels, np.int64)
+        if a.ndim == 2 and a.shape[1] == 2:
+            if ((a[:, 0] < 0) | (a[:, 0] >= self.width)).any():
+                raise RTError(RT_ERR_INVALID, "pick: x outside the frame")
+            a = a[:, 0] + a[:, 1] * self.width
+        a = a.reshape(-1)
+        if ((a < 0) | (a >= self.width * self.height)).any():
+            raise RTError(RT_ERR_INVALID, "pick: pixel outside the frame")
+        return np.ascontiguousarray(a, np.uint32)
+
+    def gbuffer_walk(self, pixels=False):
+        """What the next gbuffer() (pixels=False) or pick() (pixels=True) launches with, from where the launch
+        takes it (rt_renderer_gbuffer_walk): {"wave": True the wave camera walk / False the lane walk,
+        "lds_bytes": the launch's dynamic LDS per workgroup}."""
+        w, lds = C.c_int(), C.c_uint32()
+        _check(self.L.rt_renderer_gbuffer_walk(self.h, int(bool(pixels)), C.byref(w), C.byref(lds)))
+        return {"wave": bool(w.value), "lds_bytes": int(lds.value)}
+
+    def _query_stream(self, stream):
+        """(context, raw stream) of a query: the planes are allocated, and a host pixel list is uploaded, on
+        the stream the kernel is launched on -- torch's current stream, or the caller's raw `stream` entered
+        as torch's stream for the call -- so the upload is ordered before the launch and the caching
+        allocator knows where the planes are used."""
+        torch = _torch()
+        if stream is None:
+            return contextlib.nullcontext(), torch.cuda.current_stream(self.scene.device).cuda_stream
+        return torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=f"cuda:{self.scene.device}")), int(stream)
+
+    def _device_planes(self, planes, shape):
+        torch = _torch()
+        dev = f"cuda:{self.scene.device}"
+        t = {n: torch.empty(shape + (7 if n == "ray" else 4,), dtype=torch.float32, device=dev) for n in planes}
+        return t, GBuffer(**{n: t[n].data_ptr() for n in planes})
+
+    @staticmethod
+    def _host_planes(planes, shape):
+        a = {n: np.zeros(shape, _GBUFFER_DTYPES[n]) for n in planes}
+        return a, GBuffer(**{n: a[n].ctypes.data for n in planes})
+
+    def gbuffer(self, planes=("hit", "normal", "albedo", "ray"), rect=None, sample=0, spp=1, frame=None, stream=None):
+        """The first hit of the camera rays of sample `sample` (of `spp`) of frame `frame` (None: the
+        renderer's current frame number, which stays) over rect = (x0, y0, w, h) (None: the whole frame).
+        Returns {plane: float32 torch tensor [h, w, 4] on the device ([h, w, 7] for "ray")}: hit = t, obj
+        (int32 bits, -1 sky), u, v; normal = Scene::GetNormal flipped against the ray + the material id
+        (int32 bits); albedo = the material's GetColor / skyColor + the material kind (int32 bits, -1 sky);
+        ray = O, D, tmax as GetPrimaryRay returns it.  `.view(torch.int32)` reads the integer fields.
+        stream: a raw stream handle (None: torch's current stream); the planes are allocated on it and the
+        kernel runs on it, so work the caller queues on that stream afterwards sees the planes filled."""
+        torch = _torch()
+        planes, p = self._gbuffer_params(planes, sample, spp, frame)
+        x0, y0, w, h = self._gbuffer_rect(rect)
+        ctx, s = self._query_stream(stream)
+        with ctx:
+            t, g = self._device_planes(planes, (h, w))
+            _check(self.L.rt_render_gbuffer(self.h, C.byref(self.camera), C.byref(p), sample, x0, y0, w, h, C.byref(g),
+                                            C.c_void_p(s)))
+        return t
+
+    def gbuffer_host(self, planes=("hit", "normal", "albedo", "ray"), rect=None, sample=0, spp=1, frame=None):
+        """gbuffer() with the planes in host memory: {plane: numpy structured array [h, w]} of RAY_DTYPE,
+        HIT_DTYPE, GNORMAL_DTYPE, GALBEDO_DTYPE (synchronous)."""
+        planes, p = self._gbuffer_params(planes, sample, spp, frame)
+        x0, y0, w, h = self._gbuffer_rect(rect)
+        a, g = self._host_planes(planes, (h, w))
+        _check(self.L.rt_render_gbuffer_host(self.h, C.byref(self.camera), C.byref(p), sample, x0, y0, w, h, C.byref(g)))
+        return a
+
+    def pick(self, pixels, planes=("hit",), sample=0, spp=1, frame=None, stream=None):
+        """What lies under the listed pixels (indices x + y*W, or [n, 2] (x, y) pairs; any order,
+        duplicates allowed): gbuffer()'s planes as [n, 4] / [n, 7] tensors, row i for list entry i."""
+        torch = _torch()
+        planes, p = self._gbuffer_params(planes, sample, spp, frame)
+        ctx, s = self._query_stream(stream)
+        with ctx:
+            if isinstance(pixels, torch.Tensor) and pixels.is_cuda:   # a device list is used as it is (never read here;
+                lst = pixels.to(dtype=torch.int32).contiguous().reshape(-1)   # the caller orders its writes before `stream`)
+            else:
+                lst = torch.from_numpy(self._pixel_list(pixels).view(np.int32)).to(f"cuda:{self.scene.device}")
+            n = lst.numel()
+            t, g = self._device_planes(planes, (n,))
+            if n == 0:   # (an empty tensor has no address to hand over as a plane; the library would launch nothing)
+                return t
+            _check(self.L.rt_gbuffer_pixels(self.h, C.byref(self.camera), C.byref(p), sample, C.c_void_p(lst.data_ptr()), n,
+                                            C.byref(g), C.c_void_p(s)))
+        return t
+
+    def pick_host(self, pixels, planes=("hit",), sample=0, spp=1, frame=None):
+        """pick() with the list and the planes in host memory: {plane: numpy structured array [n]}."""
+        planes, p = self._gbuffer_params(planes, sample, spp, frame)
+        lst = self._pixel_list(pixels)
+        a, g = self._host_planes(planes, (len(lst),))
+        if len(lst):
+            _check(self.L.rt_gbuffer_pixels_host(self.h, C.byref(self.camera), C.byref(p), sample, lst.ctypes.data_as(C.c_void_p),
+                                                 len(lst), C.byref(g)))
+        return a
 
     def shard_capacity(self, num_shards):
         n = C.c_uint32()

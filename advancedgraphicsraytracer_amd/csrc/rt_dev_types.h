@@ -147,6 +147,20 @@ struct TraceArgs {
     uint32_t n, depth;
 };
 
+// First-hit G-buffer of a frame's camera rays (rt_render_gbuffer / rt_gbuffer_pixels): the frame's
+// FrameArgs give the camera, size, spp and frame number; these say which rays and where the planes go.
+struct GBufferArgs {
+    rt_ray *ray;                         // planes, each optional: list position / rectangle pixel i
+    rt_hit *hit;
+    rt_gnormal *normal;
+    rt_galbedo *albedo;
+    uint32_t sample;                     // the ray's sample: seed InitSeed(px + W*H*(sample + spp*frame))
+    uint32_t x0, y0, w, h;               // k_gbuffer: the rectangle (inside the frame), planes of stride w
+    uint32_t tx0, ty0, ntx, ntiles;      // ... and the frame tiles it touches: first column / row, columns, count
+    const uint32_t *pixels;              // k_gbuffer_pixels: pixel indices x + y*W
+    uint32_t n;                          // ... and how many
+};
+
 // Each kernel build provides the same launchers, one table each: `kcore` is compiled without
 // the extension primitives and materials (cubes, quads, quad light, TextureMaterial, non-Light
 // light materials), `kext` with them.  The host picks per scene (rt_device.hip: launchers(scene)).
@@ -163,6 +177,8 @@ struct Launchers {
                      hipStream_t st);
     void (*pt_finish)(const FrameArgs &F, const PathArgs &P, bool last, hipStream_t st);
     void (*trace)(const SceneView &S, const TraceArgs &A, const FrameVariant &v, size_t lds, hipStream_t st);
+    void (*gbuffer)(const SceneView &S, const FrameArgs &F, const GBufferArgs &G, const GBufferVariant &v, size_t lds,
+                    hipStream_t st);
 };
 namespace kext {
 const Launchers &launchers();

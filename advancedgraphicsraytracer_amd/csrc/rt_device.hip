@@ -1261,6 +1261,102 @@ int ray_call(rt_scene *s, const void *rays, void *out, uint32_t n, void *stream,
     return RT_OK;
 }
 
+// ---- first-hit G-buffer (rt_render_gbuffer, rt_gbuffer_pixels and their _host forms)
+// Refusals come in the order a caller can check them: what the arguments alone decide (here), then the
+// device, then what the renderer decides (its frame size) -- so a host without a GPU still hears about
+// a bad argument first and never has its handle looked into.
+int gbuffer_arguments(const std::string &name, const void *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                      const rt_gbuffer *out) {
+    if (!r || !cam || !p || !out) return fail(RT_ERR_INVALID, name + ": null argument");
+    if (!out->ray && !out->hit && !out->normal && !out->albedo) return fail(RT_ERR_INVALID, name + ": no plane asked for");
+    if (sample >= std::max(1u, p->spp)) return fail(RT_ERR_INVALID, name + ": sample outside the frame's samples per pixel");
+    return RT_OK;
+}
+int gbuffer_rectangle(const std::string &name, const rt_frame_params *p, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    if (!w || !h) return fail(RT_ERR_INVALID, name + ": empty rectangle");
+    if (x0 >= p->width || w > p->width - x0 || y0 >= p->height || h > p->height - y0)
+        return fail(RT_ERR_INVALID, name + ": the rectangle leaves the frame");
+    return RT_OK;
+}
+int gbuffer_device() {
+    static const bool have = [] {
+        int count = 0;
+        return hipGetDeviceCount(&count) == hipSuccess && count > 0;
+    }();
+    return have ? RT_OK : fail(RT_ERR_NO_DEVICE, "no HIP device visible: the MI355X path has no CPU fallback");
+}
+// The scene's view as a query launches with it right now -- this query's camera walk, no walk counters --
+// and the launch's dynamic LDS: the lane stacks, plus the wave walk's word stack when it runs.  The one
+// place both are decided: the launch below and rt_renderer_gbuffer_walk read it.
+SceneView gbuffer_view(const rt_renderer *r, bool pixels, size_t &lds) {
+    const rt_scene *s = r->scene;
+    SceneView view = s->view;
+    view.wave_primary = gbuffer_wave_walk({pixels, s->walk, r->wave, s->ext, s->has_cubes, s->nested, s->walk_fits}) ? 1 : 0;
+    view.walk_check = RT_WALK_CHECK_OFF;
+    view.walk_stats = nullptr;
+    lds = stack_bytes(s) + walk_bytes(s, view);
+    return view;
+}
+// The launch: the frame's record for the camera, size and seed (nothing of the renderer's frame
+// state goes into it or comes out of it), the scene's view with this query's camera walk, on the
+// caller's stream behind the scene's pending updates.
+int gbuffer_launch(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, GBufferArgs &G, bool pixels, hipStream_t st) {
+    if (int rc = gbuffer_device(); rc != RT_OK) return rc;
+    rt_frame_params q = *p;
+    q.spp = std::max(1u, p->spp);
+    q.mode = RT_MODE_PATH;
+    FrameArgs F;
+    if (int rc = frame_args(r, cam, &q, 0, 1, nullptr, 0, F); rc != RT_OK) return rc;   // (the frame size; the device)
+    F.acc = nullptr;
+    F.counters = nullptr;
+    if (pixels && G.n == 0) return RT_OK;
+    rt_scene *s = r->scene;
+    if (int rc = after_updates(s, st); rc != RT_OK) return rc;
+    size_t lds = 0;
+    const SceneView view = gbuffer_view(r, pixels, lds);
+    launchers(s).gbuffer(view, F, G, gbuffer_variant(pixels, !view.sky_const), lds, st);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+GBufferArgs gbuffer_planes(const rt_gbuffer *out, uint32_t sample) {
+    GBufferArgs G{};
+    G.ray = out->ray; G.hit = out->hit; G.normal = out->normal; G.albedo = out->albedo;
+    G.sample = sample;
+    return G;
+}
+// The _host forms' staging in the scene's buffer, on its private stream, as the batched ray calls
+// do: [pixel list] | ray | hit | normal | albedo, the asked-for planes only, 256-B aligned pieces of
+// `count` records.  `run` launches with the device planes (and the device list).
+template <class Run>
+int gbuffer_staged(rt_renderer *r, const rt_frame_params *p, const uint32_t *list, size_t count, const rt_gbuffer *out, Run run) {
+    if (int rc = gbuffer_device(); rc != RT_OK) return rc;
+    if (p->width != r->W || p->height != r->H) return fail(RT_ERR_INVALID, "frame size differs from the renderer's accumulator");
+    if (count == 0) return RT_OK;
+    rt_scene *s = r->scene;
+    HIP_TRY(hipSetDevice(s->device));
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    void *const host[4] = {out->ray, out->hit, out->normal, out->albedo};
+    const size_t elem[4] = {sizeof(rt_ray), sizeof(rt_hit), sizeof(rt_gnormal), sizeof(rt_galbedo)};
+    size_t off[4], need = list ? up(sizeof(uint32_t) * count) : 0;
+    for (int k = 0; k < 4; ++k) {
+        off[k] = need;
+        if (host[k]) need += up(elem[k] * count);
+    }
+    if (int rc = grow(&s->d_scratch, &s->scratch_bytes, need); rc != RT_OK) return rc;
+    char *b = (char *)s->d_scratch;
+    if (list) HIP_TRY(hipMemcpyAsync(b, list, sizeof(uint32_t) * count, hipMemcpyHostToDevice, s->stream));
+    rt_gbuffer dev{};
+    dev.ray = out->ray ? (rt_ray *)(b + off[0]) : nullptr;
+    dev.hit = out->hit ? (rt_hit *)(b + off[1]) : nullptr;
+    dev.normal = out->normal ? (rt_gnormal *)(b + off[2]) : nullptr;
+    dev.albedo = out->albedo ? (rt_galbedo *)(b + off[3]) : nullptr;
+    if (int rc = run((const uint32_t *)b, &dev, s->stream); rc != RT_OK) return rc;
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], b + off[k], elem[k] * count, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RT_OK;
+}
+
 }  // namespace
 
 // accumulator <-> packed [tile][64] float4 of listed tiles: one wave per tile, one lane per pixel
@@ -1630,6 +1726,61 @@ int rt_render_frame_host(rt_renderer *r, const rt_camera *cam, const rt_frame_pa
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpyAsync(rgb8, r->d_rgb, sizeof(uint32_t) * (size_t)r->W * r->H, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
+    return RT_OK;
+}
+
+int rt_render_gbuffer(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample, uint32_t x0, uint32_t y0,
+                      uint32_t w, uint32_t h, const rt_gbuffer *out, void *stream) {
+    const char *name = "rt_render_gbuffer";
+    if (int rc = gbuffer_arguments(name, r, cam, p, sample, out); rc != RT_OK) return rc;
+    if (int rc = gbuffer_rectangle(name, p, x0, y0, w, h); rc != RT_OK) return rc;
+    GBufferArgs G = gbuffer_planes(out, sample);
+    G.x0 = x0; G.y0 = y0; G.w = w; G.h = h;
+    G.tx0 = x0 / 8u; G.ty0 = y0 / 8u;
+    G.ntx = (x0 + w + 7u) / 8u - G.tx0;
+    G.ntiles = G.ntx * ((y0 + h + 7u) / 8u - G.ty0);
+    return gbuffer_launch(r, cam, p, G, false, (hipStream_t)stream);
+}
+
+int rt_render_gbuffer_host(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample, uint32_t x0,
+                           uint32_t y0, uint32_t w, uint32_t h, const rt_gbuffer *out) {
+    const char *name = "rt_render_gbuffer_host";
+    if (int rc = gbuffer_arguments(name, r, cam, p, sample, out); rc != RT_OK) return rc;
+    if (int rc = gbuffer_rectangle(name, p, x0, y0, w, h); rc != RT_OK) return rc;
+    return gbuffer_staged(r, p, nullptr, (size_t)w * h, out, [&](const uint32_t *, const rt_gbuffer *dev, hipStream_t st) {
+        return rt_render_gbuffer(r, cam, p, sample, x0, y0, w, h, dev, st);
+    });
+}
+
+int rt_gbuffer_pixels(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample, const uint32_t *pixels,
+                      uint32_t n, const rt_gbuffer *out, void *stream) {
+    const char *name = "rt_gbuffer_pixels";
+    if (int rc = gbuffer_arguments(name, r, cam, p, sample, out); rc != RT_OK) return rc;
+    if (n && !pixels) return fail(RT_ERR_INVALID, std::string(name) + ": null pixel list");
+    GBufferArgs G = gbuffer_planes(out, sample);
+    G.pixels = pixels;
+    G.n = n;
+    return gbuffer_launch(r, cam, p, G, true, (hipStream_t)stream);
+}
+
+int rt_gbuffer_pixels_host(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                           const uint32_t *pixels, uint32_t n, const rt_gbuffer *out) {
+    const char *name = "rt_gbuffer_pixels_host";
+    if (int rc = gbuffer_arguments(name, r, cam, p, sample, out); rc != RT_OK) return rc;
+    if (n && !pixels) return fail(RT_ERR_INVALID, std::string(name) + ": null pixel list");
+    for (uint32_t i = 0; i < n; ++i)
+        if (pixels[i] >= (uint64_t)p->width * p->height)
+            return fail(RT_ERR_INVALID, std::string(name) + ": pixel " + std::to_string(i) + " lies outside the frame");
+    return gbuffer_staged(r, p, pixels, n, out, [&](const uint32_t *list, const rt_gbuffer *dev, hipStream_t st) {
+        return rt_gbuffer_pixels(r, cam, p, sample, list, n, dev, st);
+    });
+}
+
+int rt_renderer_gbuffer_walk(const rt_renderer *r, int pixels, int *wave_walk, uint32_t *lds_bytes) {
+    if (!r || !wave_walk) return fail(RT_ERR_INVALID, "rt_renderer_gbuffer_walk: null argument");
+    size_t lds = 0;
+    *wave_walk = gbuffer_view(r, pixels != 0, lds).wave_primary;
+    if (lds_bytes) *lds_bytes = (uint32_t)lds;
     return RT_OK;
 }
 

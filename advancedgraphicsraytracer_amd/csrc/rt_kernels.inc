@@ -457,6 +457,7 @@ __device__ __forceinline__ const DevMaterial &hit_surface(const SceneView &S, DR
 // by field the compiler narrows each load to what its first user needs and fetches the rest where
 // the next user stands: shade .xyz + type, shade .w again, flag, kind, colour -- five trips.  The
 // empty asm keeps each group whole and where it is written.
+// (gbuffer_store below repeats these two reads to keep the material index: a change here goes there too.)
 __device__ __forceinline__ DevMaterial hit_surface_whole(const SceneView &S, DRay &ray, f3 I, f3 &N) {
     float4 s0 = S.shade[2 * ray.obj], s1 = S.shade[2 * ray.obj + 1];
     asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s0.z), "+v"(s0.w), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w));
@@ -1643,6 +1644,104 @@ __global__ __launch_bounds__(256) void k_occluded(SceneView S, const rt_ray *__r
     out[i] = occluded(S, T, r) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ first-hit G-buffer
+// The camera ray of one sample of one pixel of a frame, traced to its first hit and no further
+// (rt_render_gbuffer, rt_gbuffer_pixels): primary_ray from the frame's own seed, the closest hit,
+// finish_uv, then the surface -- Scene::GetNormal flipped against the ray and the material's
+// GetColor(ray) -- or skyColor(D).  A query: it touches nothing of F's accumulator, output, samples,
+// counters or costs, and S.walk_stats stays unread (closest_hit_primary<false> compiles no counter).
+// Which planes are stored is wave-uniform: branches on the kernel-argument pointers.  The surface costs
+// the two dependent trips of hit_surface_whole -- the shade record as two whole float4, whose .w is the
+// material id the normal plane reports, then the material as a whole record -- and is skipped
+// entirely when neither the normal nor the albedo plane is asked for.  Each 16-B record plane takes one
+// store per lane, so a tile row of 8 lanes fills one 128-B segment; the 28-B rt_ray goes out as dwords.
+template <bool TEX_SKY>
+__device__ __forceinline__ void gbuffer_store(const SceneView &S, const GBufferArgs &G, DRay &r, size_t i) {
+    finish_uv(S, r);
+    if (G.hit) {
+        rt_hit h;
+        h.t = r.t; h.obj = r.obj; h.u = r.u; h.v = r.v;
+        G.hit[i] = h;
+    }
+    if (!G.normal && !G.albedo) return;
+    rt_gnormal n;
+    rt_galbedo a;
+    if (r.obj < 0) {
+        const f3 c = sky_color<TEX_SKY>(S, r.D);
+        n.nx = 0.0f; n.ny = 0.0f; n.nz = 0.0f; n.material = -1;
+        a.r = c.x; a.g = c.y; a.b = c.z; a.kind = -1;
+    } else {
+        const f3 I = r.O + r.t * r.D;
+        // A copy of hit_surface_whole's two reads, pins included, made because that function does not hand
+        // out the material index (s0.w) and no shared function may change here: it must follow every change
+        // of hit_surface_whole, until that one returns the index and this calls it.
+        float4 s0 = S.shade[2 * r.obj], s1 = S.shade[2 * r.obj + 1];
+        asm volatile("" : "+v"(s0.x), "+v"(s0.y), "+v"(s0.z), "+v"(s0.w), "+v"(s1.x), "+v"(s1.y), "+v"(s1.z), "+v"(s1.w));
+        const int mi = __float_as_int(s0.w);
+        const float4 *mp = reinterpret_cast<const float4 *>(S.mats + mi);
+        float4 q[4] = {mp[0], mp[1], mp[2], kExt ? mp[3] : make_float4(0, 0, 0, 0)};
+        asm volatile("" : "+v"(q[0].x), "+v"(q[0].y), "+v"(q[0].z), "+v"(q[0].w), "+v"(q[1].x), "+v"(q[1].y), "+v"(q[1].z),
+                          "+v"(q[1].w), "+v"(q[2].x), "+v"(q[2].y), "+v"(q[2].z), "+v"(q[2].w));
+        if constexpr (kExt) asm volatile("" : "+v"(q[3].x), "+v"(q[3].y));
+        DevMaterial m;
+        __builtin_memcpy(&m, q, sizeof(m));
+        f3 N = prim_normal(S, s0, s1, I);              // template/scene.h:489-497
+        if (dot(N, r.D) > 0) N = -N;
+        const f3 c = mat_color(S, m, r, I);            // (the hit's u, v are final: finish_uv above)
+        n.nx = N.x; n.ny = N.y; n.nz = N.z; n.material = mi;
+        a.r = c.x; a.g = c.y; a.b = c.z; a.kind = m.kind;
+    }
+    if (G.normal) G.normal[i] = n;
+    if (G.albedo) G.albedo[i] = a;
+}
+__device__ __forceinline__ void gbuffer_store_ray(const GBufferArgs &G, const DRay &r, size_t i) {
+    if (!G.ray) return;
+    float *q = reinterpret_cast<float *>(G.ray + i);
+    q[0] = r.O.x; q[1] = r.O.y; q[2] = r.O.z; q[3] = r.D.x; q[4] = r.D.y; q[5] = r.D.z; q[6] = r.t;
+}
+
+// k_render_heat's launch shape over the frame's own tile grid -- one wave per 8x8 tile, so a wave holds
+// the 64 pixels the frame's wave holds and the wave walk sees the frame's coherence -- for the
+// G.ntiles tiles the rectangle touches (G.ntx columns from tile (G.tx0, G.ty0)).  Lanes outside the
+// rectangle (which lies inside the image) take no part in the traversal, as off-image lanes in
+// render_tile.  Camera walk: S.wave_primary, set per launch by the host (gbuffer_wave_walk); the
+// extension build has the lane walk only, as its frames do.
+template <bool TEX_SKY>
+__global__ __launch_bounds__(256) void k_gbuffer(SceneView S, FrameArgs F, GBufferArgs G) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t k = blockIdx.x * 4u + (tid >> 6);
+    if (k >= G.ntiles) return;
+    Trav<256> T{S.nodes, lds_stack + tid, S.prims};
+    const uint32_t x = (G.tx0 + k % G.ntx) * 8u + (lane & 7u), y = (G.ty0 + k / G.ntx) * 8u + (lane >> 3);
+    if (!(x >= G.x0 && x - G.x0 < G.w && y >= G.y0 && y - G.y0 < G.h)) return;
+    const uint32_t px = x + y * F.W;
+    const size_t i = (size_t)(y - G.y0) * G.w + (x - G.x0);
+    uint32_t seed = init_seed(px + F.W * F.H * (G.sample + F.spp * F.frame));
+    DRay r = primary_ray(F, x, y, seed);
+    gbuffer_store_ray(G, r, i);
+    if constexpr (kExt) closest_hit(S, T, r);
+    else closest_hit_primary(S, T, r);
+    gbuffer_store<TEX_SKY>(S, G, r, i);
+}
+
+// one lane per listed pixel, as k_intersect is laid out: the lane walk (a list's lanes are no tile).
+// An index outside the frame (the device form's list is read here only) writes nothing.
+template <bool TEX_SKY>
+__global__ __launch_bounds__(256) void k_gbuffer_pixels(SceneView S, FrameArgs F, GBufferArgs G) {
+    extern __shared__ uint32_t lds_stack[];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= G.n) return;
+    const uint32_t px = G.pixels[i];
+    if (px >= F.W * F.H) return;
+    Trav<256> T{S.nodes, lds_stack + threadIdx.x, S.prims};
+    uint32_t seed = init_seed(px + F.W * F.H * (G.sample + F.spp * F.frame));
+    DRay r = primary_ray(F, px % F.W, px / F.W, seed);
+    gbuffer_store_ray(G, r, i);
+    closest_hit(S, T, r);
+    gbuffer_store<TEX_SKY>(S, G, r, i);
+}
+
 #if RT_EXT == 0
 // ------------------------------------------------------------------ BVH analysis (scene.h:244-283)
 // Scene::BVHVisualization: the walk of closest_hit_t with leaf_closest taken out, so r.t never
@@ -2488,6 +2587,10 @@ static const void *pt_lanes_kernel(bool quad, bool tex) {
     return quad ? (tex ? (const void *)k_pt_lanes<true, true> : (const void *)k_pt_lanes<false, true>)
                 : (tex ? (const void *)k_pt_lanes<true, false> : (const void *)k_pt_lanes<false, false>);
 }
+// k_gbuffer / k_gbuffer_pixels (SceneView, FrameArgs, GBufferArgs)
+static const void *gbuffer_kernel(const GBufferVariant &v) {
+    return v.pixels ? RT_SKY(v.tex, k_gbuffer_pixels) : RT_SKY(v.tex, k_gbuffer);
+}
 #undef RT_SKY
 #undef RT_SKY_OF
 
@@ -2554,10 +2657,16 @@ static void launch_occluded(const SceneView &S, const rt_ray *rays, uint8_t *out
 static void launch_intersect_packet(const SceneView &S, const rt_ray *rays, rt_hit *hits, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(k_intersect_packet, dim3((n + 255) / 256), dim3(256), 0, st, S, rays, hits, n);
 }
+// the rectangle form: one wave per touched tile; the list form: one lane per listed pixel
+static void launch_gbuffer(const SceneView &S, const FrameArgs &F, const GBufferArgs &G, const GBufferVariant &v, size_t lds,
+                           hipStream_t st) {
+    const uint32_t grid = v.pixels ? (G.n + 255u) / 256u : (G.ntiles + 3u) / 4u;
+    launch_kernel<SceneView, FrameArgs, GBufferArgs>(gbuffer_kernel(v), dim3(grid), lds, st, S, F, G);
+}
 // (a function's static, not a namespace-scope constant: the device pass would emit that one too)
 const Launchers &launchers() {
     static const Launchers table = {launch_frame,    launch_work,     launch_intersect, launch_occluded, launch_intersect_packet,
-                                    launch_pt_level, launch_pt_lanes, launch_pt_finish, launch_trace};
+                                    launch_pt_level, launch_pt_lanes, launch_pt_finish, launch_trace,    launch_gbuffer};
     return table;
 }
 #if RT_EXT == 0

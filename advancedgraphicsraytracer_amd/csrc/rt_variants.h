@@ -86,6 +86,34 @@ constexpr FrameVariant work_variant(uint32_t depth, bool tex) {
     return FrameVariant{FrameBuild::Plain, RT_MODE_PATH, depth_class(depth) == 1 ? 1 : 32, tex};
 }
 
+// The first-hit G-buffer family (rt_render_gbuffer / rt_gbuffer_pixels): k_gbuffer, one wave per 8x8 tile
+// of the frame's own tile grid, or k_gbuffer_pixels, one lane per listed pixel; each with the constant
+// or the textured sky.  A query: no mode, no MAXD, no frame build.
+struct GBufferVariant {
+    bool pixels = false;   // k_gbuffer_pixels (a pixel list) instead of k_gbuffer (a rectangle of tiles)
+    bool tex = false;      // non-constant sky texture
+};
+constexpr GBufferVariant gbuffer_variant(bool pixels, bool tex) { return GBufferVariant{pixels, tex}; }
+constexpr const char *gbuffer_variant_name(const GBufferVariant &v) {
+    return v.pixels ? (v.tex ? "k_gbuffer_pixels<tex>" : "k_gbuffer_pixels<const>") : (v.tex ? "k_gbuffer<tex>" : "k_gbuffer<const>");
+}
+
+// what the G-buffer's camera walk reads
+struct GBufferWalkInputs {
+    bool pixels;      // the list form: its lanes are not a tile
+    int walk;         // the scene's policy, RT_WALK_*
+    int settled;      // the renderer's timed choice for its primary+shadow frames: 1 wave, 0 lane, -1 none yet
+    bool ext;         // the scene runs the extension build (its frames never take the wave walk)
+    bool has_cubes, nested, walk_fits;   // the scene's conditions of the wave walk (rt_scene_set_camera_walk)
+};
+// Camera rays of a G-buffer take the wave walk exactly where a primary+shadow frame of the same
+// renderer would right now: the scene forces it, or RT_WALK_AUTO has settled on it.  Nothing settled:
+// the lane walk -- a query starts and advances no timed choice.
+constexpr bool gbuffer_wave_walk(const GBufferWalkInputs &in) {
+    if (in.pixels || in.ext || in.has_cubes || !in.nested || !in.walk_fits) return false;
+    return in.walk == RT_WALK_WAVE || (in.walk == RT_WALK_AUTO && in.settled > 0);
+}
+
 // The public name of a frame variant's kernel (rt_frame_kernel_name; rocprofv3's, abbreviated);
 // nullptr: no such build.  It reads the class alone: the single-sample and walk-check builds of
 // <path,1> answer k_render<path,1> too -- they are builds of that kernel (same frames, same roofline

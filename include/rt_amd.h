@@ -566,6 +566,55 @@ int rt_render_frame(rt_renderer *r, const rt_camera *cam, const rt_frame_params 
 /* Same as rt_render_frame, RGB8 delivered to host memory (the reference's
  * screen->pixels, template/template.cpp:273-277); synchronous. */
 int rt_render_frame_host(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t *rgb8_host);
+
+/* ---- first-hit G-buffer of a frame's camera rays, and pixel picking ----------
+ * The camera ray of a pixel of the frame p describes -- with the sub-pixel and lens jitter of
+ * Camera::GetPrimaryRay (camera.h:43-52), drawn from the seed InitSeed(px + W*H*(sample + spp*frame))
+ * of that sample of that frame -- traced to its first hit, and what lies there.  A query: it reads and
+ * writes nothing of the renderer's frame state (accumulator, rt_counters, walk statistics, tile costs,
+ * timed choices, frames in flight), and runs on the caller's stream behind the scene's pending
+ * stream-ordered updates, as a frame does: rt_scene_update_*_async followed by rt_render_gbuffer sees the
+ * updated scene with no host synchronisation. */
+typedef struct { float nx, ny, nz; int32_t material; } rt_gnormal;  /* 16 B */
+typedef struct { float r, g, b;   int32_t kind;     } rt_galbedo;  /* 16 B */
+
+/* every plane optional (NULL = not written); at least one must be set */
+typedef struct {
+    rt_ray     *ray;     /* the camera ray as GetPrimaryRay returns it (tmax = the ray's initial t) */
+    rt_hit     *hit;     /* the ray as IntersectBVH leaves it (template/scene.h:285-320) + finish_uv: t, obj (-1 = sky), u, v */
+    rt_gnormal *normal;  /* Scene::GetNormal(obj, I, D) (template/scene.h:489-497; flipped against the ray), I = O + t*D;
+                            material = the primitive's material id; sky: 0,0,0 and -1 */
+    rt_galbedo *albedo;  /* the material's GetColor(ray) at the hit (Diffuse/Mirror/Light/DSMix colour, Checkerboard.h:28-37,
+                            TextureMaterial.h:32-39, Dielectric.h:12-21 with inside = false), kind = RT_* material kind;
+                            sky: skyColor(D) (renderer.h:15-22) and -1 */
+} rt_gbuffer;
+
+/* pixels [x0, x0+w) x [y0, y0+h) of the frame p describes; planes are rect-sized, row-major, stride w.
+ * p->width, p->height, p->spp and p->frame define the ray (spp 0 counts as 1); p->depth, p->mode and
+ * p->reset are ignored.  The camera walk is the scene's policy as a frame would take it: RT_WALK_LANE the
+ * lane walk, RT_WALK_WAVE the wave walk, RT_WALK_AUTO whatever this renderer's primary+shadow frames
+ * have settled on (the lane walk while nothing is settled; no timed choice starts or advances).
+ *   RT_ERR_INVALID  null r / cam / p / out, all four planes NULL, sample >= max(1, spp), an empty
+ *                   rectangle or one that leaves the frame, a width or height that is not the renderer's. */
+int rt_render_gbuffer(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                      uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const rt_gbuffer *out_dev, void *stream);
+/* the same with the planes in host memory (through the scene's staging buffer; synchronous) */
+int rt_render_gbuffer_host(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                           uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, const rt_gbuffer *out);
+/* picking: listed pixel indices (x + y*W, any order, duplicates allowed), planes indexed by list position;
+ * always the lane walk (a list's lanes are not a tile).  n == 0 succeeds and launches nothing.
+ *   RT_ERR_INVALID  as above, a null list with n > 0, and -- the _host form, which can read its list -- a
+ *                   pixel index >= W*H.  The device form reads its list on the GPU only: an index
+ *                   >= W*H there leaves that list position of every plane unwritten. */
+int rt_gbuffer_pixels(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                      const uint32_t *pixels_dev, uint32_t n, const rt_gbuffer *out_dev, void *stream);
+int rt_gbuffer_pixels_host(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t sample,
+                           const uint32_t *pixels, uint32_t n, const rt_gbuffer *out);
+/* What the next rt_render_gbuffer (pixels = 0) or rt_gbuffer_pixels (pixels != 0) of this renderer launches
+ * with, from the same place the launch takes it: *wave_walk = 1 the wave camera walk, 0 the lane walk;
+ * *lds_bytes (optional) the launch's dynamic LDS per workgroup -- the lane stacks, plus the wave walk's
+ * word stack when it runs.  Reads only; RT_ERR_INVALID for a null r or wave_walk. */
+int rt_renderer_gbuffer_walk(const rt_renderer *r, int pixels, int *wave_walk, uint32_t *lds_bytes);
 /* Screen-tile shard of a frame: the 8x8 tiles t with t % num_shards == shard,
  * packed as [tile][64] pixels into tiles_dev (rt_shard_capacity pixels). */
 int rt_shard_capacity(uint32_t width, uint32_t height, uint32_t num_shards, uint32_t *pixels);

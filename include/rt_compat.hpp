@@ -495,6 +495,36 @@ class Renderer : public TheApp {   // renderer.h:5-160
     }
     uint32_t seed = 0x12345678;     // template/template.cpp:673
 
+    // The first-hit G-buffer of the frame last shown by Tick (before the first Tick: of frame 0) -- per
+    // pixel the camera ray of `sample` of its `spp`, the hit IntersectBVH leaves, Scene::GetNormal and the
+    // material's GetColor -- row-major, width x height (rt_render_gbuffer_host).  Changes no frame state.
+    struct GBufferPlanes {
+        std::vector<rt_ray> ray;
+        std::vector<rt_hit> hit;
+        std::vector<rt_gnormal> normal;
+        std::vector<rt_galbedo> albedo;
+    };
+    GBufferPlanes GBuffer(uint32_t sample = 0, uint32_t spp = 1) {
+        if (!h_) Init();
+        const size_t n = (size_t)width_ * height_;
+        GBufferPlanes g{std::vector<rt_ray>(n), std::vector<rt_hit>(n), std::vector<rt_gnormal>(n), std::vector<rt_galbedo>(n)};
+        const rt_frame_params p{width_, height_, spp, 1u, frame_ ? frame_ - 1u : 0u, RT_MODE_PATH, 0u};
+        const rt_gbuffer out{g.ray.data(), g.hit.data(), g.normal.data(), g.albedo.data()};
+        rt_check(rt_render_gbuffer_host(h_, &camera.cam, &p, sample, 0u, 0u, width_, height_, &out));
+        return g;
+    }
+    // Picking: what lies under pixel (x, y) of that frame -- t, obj (-1 = sky), u, v
+    rt_hit Pick(uint32_t x, uint32_t y, uint32_t sample = 0, uint32_t spp = 1) {
+        if (!h_) Init();
+        if (x >= width_ || y >= height_) throw RtError(RT_ERR_INVALID, "Pick: pixel outside the frame");
+        const uint32_t px = x + y * width_;
+        rt_hit h{};
+        const rt_frame_params p{width_, height_, spp, 1u, frame_ ? frame_ - 1u : 0u, RT_MODE_PATH, 0u};
+        const rt_gbuffer out{nullptr, &h, nullptr, nullptr};
+        rt_check(rt_gbuffer_pixels_host(h_, &camera.cam, &p, sample, &px, 1u, &out));
+        return h;
+    }
+
     // The K key (renderer.h:138): switch integrators; the next frame restarts accumulation.
     void ToggleWhitted() { useWhitted = !useWhitted; tracerSwap = true; }
     rt_counters Counters() { rt_counters c{}; rt_check(rt_renderer_counters(h_, &c)); return c; }
