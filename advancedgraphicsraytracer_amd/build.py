@@ -15,7 +15,7 @@ LIB = os.path.join(PKG, "librtamd.so")
 # the kernels are compiled twice (core / extension builds of rt_kernels.inc), in parallel
 SOURCES = ["rt_host.cpp", "rt_device.hip", "rt_kern_core.hip", "rt_kern_ext.hip", "rt_multi.cpp", "rt_sbvh.cpp",
            "rt_refit.hip", "rt_build.hip", "rt_splice.hip", "rt_scene_pack.cpp", "rt_cost.hip", "rt_plan.hip", "rt_scene_edit.hip"]
-HEADERS = ["rt_math.h", "rt_internal.h", "rt_libm.h", "rt_dev_types.h", "rt_variants.h", "rt_kernels.inc", "rt_refit.h", "rt_tune.h",
+HEADERS = ["rt_math.h", "rt_internal.h", "rt_libm.h", "rt_dev_types.h", "rt_variants.h", "rt_kernels.inc", "rt_refit.h", "rt_tune.h", "rt_sched.h",
            "rt_records.h", "rt_update.h", "rt_build.h", "rt_splice.h", "rt_cost.h", "rt_plan.h", "rt_scene.h", os.path.join("..", "..", "include", "rt_amd.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

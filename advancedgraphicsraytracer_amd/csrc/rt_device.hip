@@ -38,6 +38,7 @@
 #include "rt_records.h"
 #include "rt_refit.h"
 #include "rt_scene.h"
+#include "rt_sched.h"
 #include "rt_tune.h"
 
 // ====================================================================== host side
@@ -57,6 +58,39 @@ inline int hw_queues() {
     return v > 0 ? v : 4;
 }
 
+// A ring of N frame-level result buffers ([sample][pixel] radiance), frame n in buffer n % (the
+// count in use): each with the event of the finishing pass that last read it, which the next frame
+// to write the buffer waits for, and whether that event was recorded since the buffer was made.
+// With as many buffers as frames in flight, frame n + 2's kernels waited for frame n's finishing
+// pass, which itself follows frame n + 1's kernels on the caller's stream; one buffer more lets a
+// frame start behind the finish of the frame `count` back.
+template <int N>
+struct ResultRing {
+    DevBuf buf[N];
+    hipEvent_t fin[N] = {};
+    bool fin_set[N] = {};
+
+    int event(int b) {   // fin[b], created as first needed
+        if (!fin[b]) HIP_TRY(hipEventCreateWithFlags(&fin[b], hipEventDisableTiming | hipEventReleaseToDevice));
+        return RT_OK;
+    }
+    // buffer b grown to `bytes`, after every pending use of the old one
+    int ensure(int b, size_t bytes) {
+        if (bytes <= buf[b].bytes) return RT_OK;
+        fin_set[b] = false;
+        return buf[b].grow(bytes, Wait::kDevice);
+    }
+    // buffers k .. N-1 freed (the caller knows that nothing uses them)
+    int drop_from(int k) {
+        for (int b = k; b < N; ++b) {
+            if (int rc = buf[b].release(); rc != RT_OK) return rc;
+            fin_set[b] = false;
+        }
+        return RT_OK;
+    }
+    float4 *at(int b) const { return buf[b].template as<float4>(); }
+};
+
 struct rt_renderer {
     rt_scene *scene = nullptr;
     int device = 0;             // the scene's device, for rt_renderer_destroy: a caller (Python's
@@ -69,7 +103,7 @@ struct rt_renderer {
     hipStream_t stream = nullptr;
     // measured-cost tile order (tile_order_step): per-tile cycles of one frame (two cost
     // maps while the camera walk is being timed), longest tile first afterwards
-    uint32_t *d_order = nullptr, *d_cost = nullptr;
+    DevBuf d_order, d_cost;
     std::vector<uint32_t> host_cost;   // the cost map the active order was sorted from (local tiles)
     bool tail_bound = false;    // that map's costliest tile outlasts 2 x the frame's mean time per
                                 // resident wave slot: frames in flight beyond 2 become candidates
@@ -98,12 +132,10 @@ struct rt_renderer {
     // buffer (two, by frame parity); one finishing pass per frame on the caller's stream sums
     // it in sample order after every batch's levels (accumulator, RGB8).  d_pt[0] / the
     // caller's stream alone when pipelining is off or the results do not fit.
-    void *d_pt[kPtMaxSlots] = {};
-    size_t pt_bytes[kPtMaxSlots] = {};
+    DevBuf d_pt[kPtMaxSlots];
     // [sample][pixel] radiance of a frame, frame n in buffer n % (slots + 1): frame n + slots + 1's
     // batches wait for frame n's finishing pass only (see launch_pt_frame)
-    float4 *d_res[kPtMaxSlots + 1] = {};
-    size_t res_bytes[kPtMaxSlots + 1] = {};
+    ResultRing<kPtMaxSlots + 1> pt_res;
     float4 *d_sum = nullptr;        // the running sample sum across batches (serial path)
     // renderer streams: the path tracer's two path streams are 0 and 1; overlapped primary+
     // shadow frames use the first `depth` of them (frames in flight)
@@ -111,8 +143,6 @@ struct rt_renderer {
     int nstreams = 0;               // pt_stream[0 .. nstreams) created (ensure_pipe_streams)
 
     hipEvent_t pt_lv[kPsMaxDepth] = {};   // a renderer stream's work of this frame is done
-    hipEvent_t pt_fin[kPtMaxSlots + 1] = {};   // the finish that read d_res[b] is done
-    bool pt_fin_set[kPtMaxSlots + 1] = {};
     int pt_slot = 0, pt_parity = 0;
     uint32_t pt_nslots = 0;         // slots in use, decided for path state of up to pt_need bytes
     size_t pt_need = 0;
@@ -128,10 +158,7 @@ struct rt_renderer {
     // the overlapped frames' per-sample results, frame n in buffer n % buffers (kernel on
     // renderer stream n % depth): frame n + buffers waits for the finishing pass of frame n only,
     // so a kernel never waits for the finish of a frame still running beside it
-    float4 *ps_res[kPsMaxDepth + 1] = {};
-    size_t ps_res_bytes[kPsMaxDepth + 1] = {};
-    hipEvent_t ps_fin[kPsMaxDepth + 1] = {};
-    bool ps_fin_set[kPsMaxDepth + 1] = {};
+    ResultRing<kPsMaxDepth + 1> ps_res;
     uint32_t ps_count = 0;
     // tuning gate: the timed choices (camera walk, split order, frames in flight) of a parameter
     // set start once its frames have run tune_delay_ms of GPU time -- an event at its first frame
@@ -140,8 +167,7 @@ struct rt_renderer {
     int gate_state = 0;             // 0 start, 1 running, 2 probe recorded, 3 open
     uint32_t gate_frames = 0;
     // per-sample values of sample-split frames (FrameArgs::samples)
-    void *d_samples = nullptr;
-    size_t samples_bytes = 0;
+    DevBuf d_samples;
     // explicit tile deal of rt_render_shard_tiles (FrameArgs::tile_map): local -> global tile,
     // uploaded when it changes; and rank 0's per-global-tile (shard << 24 | local) for assembly
     std::vector<uint32_t> map_host;
@@ -152,15 +178,23 @@ struct rt_renderer {
     uint32_t held_shard = 0, held_nshards = 1;
     std::vector<uint32_t> held_list;
     uint64_t map_gen = 0, held_gen = 0;   // set_tile_map's changes; the one held_list was copied at
-    uint32_t *d_work = nullptr;     // dry-run work frame: per local tile (work_frame)
-    uint32_t work_cap = 0;
-    uint32_t *d_map = nullptr;
-    size_t map_cap = 0;
+    DevBuf d_work;                  // dry-run work frame: per local tile (work_frame)
+    DevBuf d_map;
     uint64_t map_hash = 0;
-    uint32_t *d_where = nullptr;
-    size_t where_cap = 0;
+    DevBuf d_where;
     uint64_t where_hash = 0;
+    TileGrid grid() const { return tile_grid(W, H); }
 };
+
+// every growable buffer the renderer owns (the accumulator, the counters, d_rgb and d_sum are
+// allocated once, at their one size): rt_renderer_destroy frees them, rt_renderer_device_bytes sums them
+template <class R, class Fn>
+void each_buffer(R &r, Fn f) {
+    for (auto &b : r.d_pt) f(b);
+    for (auto &b : r.pt_res.buf) f(b);
+    for (auto &b : r.ps_res.buf) f(b);
+    for (auto *b : {&r.d_samples, &r.d_order, &r.d_cost, &r.d_map, &r.d_work, &r.d_where}) f(*b);
+}
 
 namespace {
 
@@ -350,22 +384,12 @@ size_t walk_bytes(const rt_scene *s, const SceneView &v) {
 // the scene's kernel family: the extension build where the scene holds what only it knows
 const Launchers &launchers(const rt_scene *s) { return s->ext ? kext::launchers() : kcore::launchers(); }
 // pixels covered by a frame / shard launch (primary rays per sample)
-uint64_t frame_pixels(const rt_renderer *r, const FrameArgs &F, uint32_t shard, uint32_t nshards, uint32_t tiles_x,
-                      uint32_t ntiles) {
-    uint64_t px = (uint64_t)F.ntiles_local * 64u;
-    if ((r->W & 7u) || (r->H & 7u)) {
-        px = 0;
-        auto add = [&](uint32_t t) {
-            uint32_t tx = t % tiles_x, ty = t / tiles_x;
-            px += (uint64_t)std::min(8u, r->W - tx * 8) * std::min(8u, r->H - ty * 8);
-        };
-        if (F.tile_map)
-            for (uint32_t t : r->map_host) add(t);
-        else
-            for (uint32_t t = shard; t < ntiles; t += nshards) add(t);
-    }
-    return px;
+uint64_t frame_pixels(const rt_renderer *r, const FrameArgs &F) {
+    return rt::frame_pixels(r->W, r->H, F.ntiles_local, F.shard, F.nshards, F.tile_map ? r->map_host.data() : nullptr);
 }
+
+// d_sum: one float4 per pixel of every tile of the frame
+size_t sum_bytes(const rt_renderer *r) { return (size_t)r->grid().ntiles * 64u * sizeof(float4); }
 
 uint64_t fnv1a(const void *d, size_t n, uint64_t h = 1469598103934665603ull) {
     const unsigned char *c = static_cast<const unsigned char *>(d);
@@ -379,7 +403,7 @@ uint64_t fnv1a(const void *d, size_t n, uint64_t h = 1469598103934665603ull) {
 // the list could repeat after its owner was freed and reallocated, and the range /
 // duplicate checks below must see every list that differs.
 int set_tile_map(rt_renderer *r, const uint32_t *tiles, uint32_t n, uint32_t ntiles) {
-    if (r->d_map && r->map_host.size() == n && (n == 0 || std::memcmp(r->map_host.data(), tiles, sizeof(uint32_t) * n) == 0))
+    if (r->d_map.p && r->map_host.size() == n && (n == 0 || std::memcmp(r->map_host.data(), tiles, sizeof(uint32_t) * n) == 0))
         return RT_OK;
     const uint64_t h = fnv1a(tiles, sizeof(uint32_t) * n, fnv1a(&n, sizeof(n)));
     std::vector<uint8_t> seen(ntiles, 0);
@@ -388,25 +412,13 @@ int set_tile_map(rt_renderer *r, const uint32_t *tiles, uint32_t n, uint32_t nti
         seen[tiles[i]] = 1;
     }
     HIP_TRY(hipDeviceSynchronize());
-    if (n > r->map_cap || !r->d_map) {
-        if (r->d_map) HIP_TRY(hipFree(r->d_map));
-        r->d_map = nullptr;
-        r->map_cap = 0;
-        HIP_TRY(hipMalloc(&r->d_map, sizeof(uint32_t) * std::max<size_t>(n, 1)));
-        r->map_cap = std::max<size_t>(n, 1);
-    }
-    if (n) HIP_TRY(hipMemcpy(r->d_map, tiles, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    if (int rc = r->d_map.grow(sizeof(uint32_t) * std::max<size_t>(n, 1)); rc != RT_OK) return rc;   // (never empty: null = no deal)
+    if (n) HIP_TRY(hipMemcpy(r->d_map.p, tiles, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     r->map_host.assign(tiles, tiles + n);
     r->map_hash = h;
     r->map_gen += 1;
     return RT_OK;
 }
-
-
-// Per-sample result buffers of pipelined path-traced frames: with two slots and two buffers
-// (by frame parity), frame n + 2's batches waited for frame n's finishing pass, which itself
-// follows frame n + 1's levels on the caller's stream; slots + 1 buffers let a frame start
-// behind the finish of the frame `slots` back.
 
 // The first n timing events of a row of rt_renderer::tune_ev, created as first needed.
 int ensure_events(hipEvent_t *ev, int n) {
@@ -428,9 +440,9 @@ int group_times(const hipEvent_t *ev, int groups, float *ms) {
 // 2.5-3.1 / 2.2 ms against 1.5 / 1.6 for the last two (round 5, profiles/r05/hwq).
 int ensure_pipe_streams(rt_renderer *r, int n) {
     n = std::min(n, kPsMaxDepth);
-    if (!r->pt_fin[0])
+    if (!r->pt_res.fin[0])
         for (int k = 0; k <= kPtMaxSlots; ++k)
-            HIP_TRY(hipEventCreateWithFlags(&r->pt_fin[k], hipEventDisableTiming | hipEventReleaseToDevice));
+            if (int rc = r->pt_res.event(k); rc != RT_OK) return rc;
     for (int k = r->nstreams; k < n; ++k) {
         HIP_TRY(hipStreamCreateWithFlags(&r->pt_stream[k], hipStreamNonBlocking));
         // ordering between streams of this device only: a device-scope release
@@ -440,31 +452,10 @@ int ensure_pipe_streams(rt_renderer *r, int n) {
     return RT_OK;
 }
 
-// The frame-level per-sample result buffer of parity `par`, grown to `bytes`.
-int ensure_res(rt_renderer *r, int par, uint64_t bytes) {
-    if (bytes <= r->res_bytes[par]) return RT_OK;
-    HIP_TRY(hipDeviceSynchronize());   // every pending use of the old buffer
-    if (r->d_res[par]) HIP_TRY(hipFree(r->d_res[par]));
-    r->d_res[par] = nullptr;
-    r->res_bytes[par] = 0;
-    r->pt_fin_set[par] = false;
-    HIP_TRY(hipMalloc(&r->d_res[par], bytes));
-    r->res_bytes[par] = bytes;
-    return RT_OK;
-}
-
-// Overlapped primary+shadow frames' result buffer b, grown to `bytes` (overlap_step).
+// Overlapped primary+shadow frames' result buffer b and its event, grown to `bytes` (overlap_step).
 int ensure_ps_res(rt_renderer *r, uint32_t b, uint64_t bytes) {
-    if (!r->ps_fin[b]) HIP_TRY(hipEventCreateWithFlags(&r->ps_fin[b], hipEventDisableTiming | hipEventReleaseToDevice));
-    if (bytes <= r->ps_res_bytes[b]) return RT_OK;
-    HIP_TRY(hipDeviceSynchronize());   // every pending use of the old buffer
-    if (r->ps_res[b]) HIP_TRY(hipFree(r->ps_res[b]));
-    r->ps_res[b] = nullptr;
-    r->ps_res_bytes[b] = 0;
-    r->ps_fin_set[b] = false;
-    HIP_TRY(hipMalloc(&r->ps_res[b], bytes));
-    r->ps_res_bytes[b] = bytes;
-    return RT_OK;
+    if (int rc = r->ps_res.event((int)b); rc != RT_OK) return rc;
+    return r->ps_res.ensure((int)b, bytes);
 }
 
 // Wavefront path tracing of one frame / shard (PathArgs, rt_dev_types.h): the samples are
@@ -485,25 +476,14 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
     // parity, up to 2 GB each); the serial path keeps them per batch with a running sum
     const uint64_t res_need = (uint64_t)F.spp * npix * 16u;
     const bool pipe = s->pt_pipeline && res_need <= (2ull << 30);
-    const uint64_t per_path = 32u + 16u + 8u + (uint64_t)(F.depth - 1) * 32u;
     // per slot: two slots of up to RT_PT_MEM_MB each when pipelined (fewer, larger batches and
     // frame-to-frame overlap beat more batches: CFG5-sub 8.85 ms with half the budget per slot
     // -- two batches a frame -- vs 8.51 ms with one batch a frame, profiles/r02/bench_pipe_*)
-    const uint64_t budget = s->pt_mem_bytes;
-    uint64_t batch = std::max<uint64_t>(1, budget / (per_path * npix));
-    batch = std::min<uint64_t>(batch, F.spp);
-    if (batch * npix > 0xffffffffull / 2) batch = std::max<uint64_t>(1, (0xffffffffull / 2) / npix);
-    const uint64_t np = batch * npix;
-    // queue segment k takes the survivors of chunks j = k (mod kQueueSegs); the grid's
-    // wave count is a multiple of kQueueSegs, so a segment never gets more than this
-    const uint64_t seg_cap = ((np / 64u + kQueueSegs - 1) / kQueueSegs + 1) * 64u;
-    const size_t qbytes = (size_t)seg_cap * kQueueSegs * 4u;
-    const size_t cbytes = (size_t)(F.depth + 1) * (2u * kQueueSegs) * 64u;   // queue counts + head counters
-    const size_t need = (size_t)(np * (per_path - 8u) + 2 * qbytes + cbytes + 4096u);
-    if (!r->d_sum) {   // one float4 per pixel of the whole frame (a shard uses its first npix)
-        const size_t tiles = (size_t)((r->W + 7) / 8) * ((r->H + 7) / 8);
-        HIP_TRY(hipMalloc(&r->d_sum, tiles * 64u * sizeof(float4)));
-    }
+    const PathPlan plan = path_plan(F.spp, F.depth, npix, s->pt_mem_bytes, kQueueSegs);
+    const uint64_t batch = plan.batch, np = plan.np, seg_cap = plan.seg_cap;
+    const size_t qbytes = plan.qbytes, cbytes = plan.cbytes, need = plan.need;
+    if (!r->d_sum)   // one float4 per pixel of the whole frame (a shard uses its first npix)
+        HIP_TRY(hipMalloc(&r->d_sum, sum_bytes(r)));
     int par = 0;
     // slot 0 was last written on the caller's stream (a serial frame): that work is done before
     // a path stream takes the slot over (a rare switch: frames whose results exceed the buffer)
@@ -518,36 +498,20 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
             size_t free_b = 0, total_b = 0;
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
             double avail = (double)free_b;
-            for (size_t b : r->pt_bytes) avail += (double)b;
-            // a frame of a few M paths (a multi-GPU rank's 1/8 of config 5: 4.1 M) is as long as
-            // its deep paths' latency chain, and 8 frames in flight overlap more of it (1/8 shard
-            // 1.24 -> 1.16-1.18 ms); whole 1080p x 16 spp frames lose with more than 4 (7.51 ->
-            // 7.61 / 7.72 ms with 6 / 8; profiles/r04/slots)
-            // (measured with GPU_MAX_HW_QUEUES=8, as bench.py runs path-traced and multi-GPU
-            // workloads; with HIP's default of 4 queues eight slot streams share them and the
-            // measurement does not carry over, so the small-batch default is 8 only when the
-            // process has at least 8 hardware queues -- ADVICE r4)
-            uint32_t k = s->pt_slots ? s->pt_slots : (np <= (8400u << 10) && hw_queues() >= 8 ? 8u : 4u);
-            while (k > 2 && (double)k * need + (8ull << 30) > avail) --k;
-            for (uint32_t j = k; j < (uint32_t)kPtMaxSlots; ++j) {
-                if (r->d_pt[j]) HIP_TRY(hipFree(r->d_pt[j]));
-                r->d_pt[j] = nullptr;
-                r->pt_bytes[j] = 0;
-            }
-            for (uint32_t j = k + 1; j <= (uint32_t)kPtMaxSlots; ++j) {
-                if (r->d_res[j]) HIP_TRY(hipFree(r->d_res[j]));
-                r->d_res[j] = nullptr;
-                r->res_bytes[j] = 0;
-            }
+            for (const DevBuf &b : r->d_pt) avail += (double)b.bytes;
+            const uint32_t k = path_slots(s->pt_slots, np, hw_queues(), need, avail);
+            for (uint32_t j = k; j < (uint32_t)kPtMaxSlots; ++j)
+                if ((rc = r->d_pt[j].release()) != RT_OK) return rc;
+            if ((rc = r->pt_res.drop_from((int)k + 1)) != RT_OK) return rc;
             r->pt_nslots = k;
             r->pt_need = need;
             r->pt_slot = r->pt_parity = 0;
-            for (bool &f : r->pt_fin_set) f = false;
+            for (bool &f : r->pt_res.fin_set) f = false;
         }
         par = r->pt_parity;
         r->pt_parity = (par + 1) % (int)(r->pt_nslots + 1);
         if ((rc = ensure_pipe_streams(r, (int)r->pt_nslots)) != RT_OK) return rc;
-        if ((rc = ensure_res(r, par, res_need)) != RT_OK) return rc;
+        if ((rc = r->pt_res.ensure(par, res_need)) != RT_OK) return rc;
     }
     bool used[kPtMaxSlots] = {};
     const size_t lds = stack_bytes(s);
@@ -559,21 +523,15 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
         if (pipe) r->pt_slot = (r->pt_slot + 1) % (int)r->pt_nslots;
         hipStream_t X = pipe ? r->pt_stream[k] : st;
         const size_t slot_need = need + (pipe ? 0 : (size_t)np * 16u + 256u);   // serial: + the results
-        if (slot_need > r->pt_bytes[k]) {
-            HIP_TRY(hipStreamSynchronize(X));   // the slot's previous batch is done with it
-            if (r->d_pt[k]) HIP_TRY(hipFree(r->d_pt[k]));
-            r->d_pt[k] = nullptr;
-            r->pt_bytes[k] = 0;
-            HIP_TRY(hipMalloc(&r->d_pt[k], slot_need));
-            r->pt_bytes[k] = slot_need;
-        }
+        // (a slot that grows waits for X: the slot's previous batch is done with it)
+        if (int rc = r->d_pt[k].grow(slot_need, Wait::kStream, X); rc != RT_OK) return rc;
         // this frame's results buffer was last read by the finish of two frames ago
-        if (pipe && !used[k] && r->pt_fin_set[par]) HIP_TRY(hipStreamWaitEvent(X, r->pt_fin[par], 0));
+        if (pipe && !used[k] && r->pt_res.fin_set[par]) HIP_TRY(hipStreamWaitEvent(X, r->pt_res.fin[par], 0));
         if (pipe && !used[k] && tile_cost) HIP_TRY(hipStreamWaitEvent(X, r->cost_ev, 0));   // the cleared cost map
         if (pipe && !used[k])
             if (int rc = after_updates(s, X); rc != RT_OK) return rc;   // (serial: launch_render's wait on st)
         used[k] = true;
-        char *b = static_cast<char *>(r->d_pt[k]);
+        char *b = r->d_pt[k].as<char>();
         auto take = [&](size_t bytes) { char *q = b; b += (bytes + 255u) & ~(size_t)255u; return q; };
         PathArgs P{};
         P.state = reinterpret_cast<float4 *>(take(np * 32u));
@@ -585,7 +543,7 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
         P.dynamic = s->pt_dynamic ? 1 : 0;
         P.rec = reinterpret_cast<float4 *>(take((size_t)(F.depth - 1) * np * 32u));
         // per-path radiance, indexed (sample - s0) * npix + pixel
-        P.result = pipe ? r->d_res[par] + (size_t)s0 * npix : reinterpret_cast<float4 *>(take(np * 16u));
+        P.result = pipe ? r->pt_res.at(par) + (size_t)s0 * npix : reinterpret_cast<float4 *>(take(np * 16u));
         P.sum = r->d_sum;
         P.tile_cost = tile_cost;
         uint32_t dlevel = drain_level;   // this batch's (a small batch drains from pt_drain_small on)
@@ -627,86 +585,16 @@ int launch_pt_frame(rt_renderer *r, const FrameArgs &F, SceneView view, bool tex
                 HIP_TRY(hipStreamWaitEvent(st, r->pt_lv[k], 0));
             }
         PathArgs P{};
-        P.result = r->d_res[par];
+        P.result = r->pt_res.at(par);
         P.sum = r->d_sum;
         P.s0 = 0;
         P.batch_spp = F.spp;
         K.pt_finish(F, P, true, st);
-        HIP_TRY(hipEventRecord(r->pt_fin[par], st));
-        r->pt_fin_set[par] = true;
+        HIP_TRY(hipEventRecord(r->pt_res.fin[par], st));
+        r->pt_res.fin_set[par] = true;
     }
     HIP_TRY(hipGetLastError());
     return RT_OK;
-}
-
-// Longest-tile-first dispatch (LPT): tiles differ in cost by an order of magnitude (sky vs
-// mesh), and the dispatcher hands out workgroups in index order, so expensive tiles that come
-// last leave most CUs idle at the end of the frame.  Each tile's wave cycles are recorded on
-// one frame, sorted on the host once, and from the next frame on slot i renders the i-th most
-// expensive tile -- for as long as camera, size, spp, depth, mode and shard stay the same.
-// With the RT_WALK_AUTO camera walk still being timed, the two timed frames record the costs
-// under each walk and the frame that picks the walk applies the matching order (active from
-// the 4th frame); otherwise frame 1 records and frame 2 applies.  Pixel values do not depend
-// on the order.  walk_phase: -1 no walk timing pending, 0 / 1 this frame times the lane /
-// wave walk, 2 the walk was picked on this frame, 3 the timing has not started yet.
-// XCD-grouped measured order (RT_XCD_ORDER=1): the frame kernel's block b (4 waves = slots
-// 4b .. 4b+3) runs on the XCD of blocks b % 8 (blocks are dealt round-robin over the 8 XCDs,
-// MI355X_MICROARCH.md), so group g = b % 8 gets one compact screen region -- a run of the
-// tiles in Morton order holding 1/8 of the measured cost -- costliest tile first.  Each XCD's
-// L2 then holds the nodes of its region only, not of the whole frame.  A group whose region
-// ran out takes tiles from the region with the most cost left.
-std::vector<uint32_t> xcd_grouped_order(const FrameArgs &F, const uint32_t *map, const std::vector<uint32_t> &entries,
-                                        const std::vector<uint32_t> &cost, uint32_t parts) {
-    // entries: order entries (local tile | split bits); an entry's cost is its tile's, divided
-    // by the parts of a split tile (bit 31)
-    const uint32_t n = (uint32_t)entries.size();
-    auto morton = [](uint32_t x, uint32_t y) {
-        uint64_t m = 0;
-        for (int b = 0; b < 16; ++b) m |= (uint64_t)((x >> b) & 1u) << (2 * b) | (uint64_t)((y >> b) & 1u) << (2 * b + 1);
-        return m;
-    };
-    std::vector<uint32_t> z(n);
-    std::vector<uint64_t> code(n);
-    std::vector<double> ec(n);
-    double total = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t e = entries[i], lt = e & 0x0fffffffu;
-        const uint32_t tile = map ? map[lt] : lt * F.nshards + F.shard;
-        code[i] = morton(tile % F.tiles_x, tile / F.tiles_x) * 16u + (e >> 28);
-        ec[i] = (e >> 31) ? cost[lt] / (double)parts : (double)cost[lt];
-        z[i] = i;
-        total += ec[i];
-    }
-    std::stable_sort(z.begin(), z.end(), [&](uint32_t a, uint32_t b) { return code[a] < code[b]; });
-    std::vector<std::vector<uint32_t>> region(8);
-    std::vector<double> left(8, 0.0);
-    double acc = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t g = std::min<uint32_t>(7u, (uint32_t)(acc * 8.0 / std::max(total, 1.0)));
-        region[g].push_back(z[i]);
-        left[g] += ec[z[i]];
-        acc += ec[z[i]];
-    }
-    for (auto &rg : region)   // costliest first within a region (sorted ascending: taken from the back)
-        std::stable_sort(rg.begin(), rg.end(), [&](uint32_t a, uint32_t b) { return ec[a] < ec[b]; });
-    std::vector<uint32_t> out;
-    out.reserve(n);
-    for (uint32_t b = 0; out.size() < n; ++b) {
-        for (uint32_t w = 0; w < 4 && out.size() < n; ++w) {
-            uint32_t g = b % 8u;
-            if (region[g].empty()) {   // out.size() < n: some region still holds entries
-                int best = -1;
-                for (uint32_t h = 0; h < 8; ++h)
-                    if (!region[h].empty() && (best < 0 || left[h] > left[best])) best = (int)h;
-                g = (uint32_t)best;
-            }
-            const uint32_t i = region[g].back();
-            region[g].pop_back();
-            left[g] -= ec[i];
-            out.push_back(entries[i]);
-        }
-    }
-    return out;
 }
 
 // The tile costs and the order of parameter set `key` with n local tiles: a new set drops what the
@@ -716,17 +604,14 @@ int ensure_order(rt_renderer *r, uint64_t key, uint32_t n) {
     r->order_key = key;
     r->order_state = 0;
     r->host_cost.clear();
-    if (n != r->order_n) {
+    if (n != r->order_n) {   // (a smaller count too: the buffers are exactly the set's)
         HIP_TRY(hipDeviceSynchronize());                             // frames may still read them
-        if (r->d_order) HIP_TRY(hipFree(r->d_order));
-        if (r->d_cost) HIP_TRY(hipFree(r->d_cost));
-        r->d_order = r->d_cost = nullptr;
         r->order_n = 0;
-        // plain order (n) | split order: n + (parts - 1) x the split tiles -- up to 9 n with 8 parts
-        // and every tile split (RT_SPLIT_PARTS / RT_SPLIT_HEAVY; 3 n overflowed a balanced rank's
-        // short tile list with 4 parts and 500 split tiles, round 5)
-        HIP_TRY(hipMalloc(&r->d_order, 9u * n * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&r->d_cost, 2u * n * sizeof(uint32_t)));   // one cost map per camera walk
+        int rc = r->d_order.release();
+        if (rc == RT_OK) rc = r->d_cost.release();
+        if (rc == RT_OK) rc = r->d_order.grow(order_capacity(n) * sizeof(uint32_t));
+        if (rc == RT_OK) rc = r->d_cost.grow(2u * (size_t)n * sizeof(uint32_t));   // one cost map per camera walk
+        if (rc != RT_OK) return rc;
         r->order_n = n;
     }
     return RT_OK;
@@ -742,6 +627,14 @@ struct FramePlan {
     uint32_t depth = 0, buf = 0, lane = 0;      // frames in flight (0 serial, else 2..6); result buffer, renderer stream
 };
 
+// The measured-cost tile order (build_tile_order, rt_sched.h): each tile's wave cycles are recorded on
+// one frame, sorted on the host once, and from the next frame on slot i renders the i-th most
+// expensive tile -- for as long as camera, size, spp, depth, mode and shard stay the same.
+// With the RT_WALK_AUTO camera walk still being timed, the two timed frames record the costs
+// under each walk and the frame that picks the walk applies the matching order (active from
+// the 4th frame); otherwise frame 1 records and frame 2 applies.  Pixel values do not depend
+// on the order.  walk_phase: -1 no walk timing pending, 0 / 1 this frame times the lane /
+// wave walk, 2 the walk was picked on this frame, 3 the timing has not started yet.
 int tile_order_step(rt_renderer *r, FrameArgs &F, bool split_ok, FramePlan &P) {
     const uint32_t n = F.ntiles_local;
     // the walk: costs recorded on this frame (0 / 1), decided on it (2), still to be timed (3)
@@ -752,13 +645,14 @@ int tile_order_step(rt_renderer *r, FrameArgs &F, bool split_ok, FramePlan &P) {
         r->ps_use = -1;
     }
     if (int rc = ensure_order(r, P.key, n); rc != RT_OK) return rc;
+    uint32_t *const d_cost = r->d_cost.as<uint32_t>(), *const d_order = r->d_order.as<uint32_t>();
     int use = -1;                                                      // cost map to sort this frame
     if (walk_phase == 3) {
         // walk timing not started yet: record nothing
     } else if (r->order_state == 0) {
-        if (walk_phase == 0 || walk_phase == 1) F.tile_cost = r->d_cost + (size_t)walk_phase * n;
+        if (walk_phase == 0 || walk_phase == 1) F.tile_cost = d_cost + (size_t)walk_phase * n;
         else if (walk_phase == 2) use = r->wave;                      // recorded on the timed frames
-        else { F.tile_cost = r->d_cost; r->order_state = 1; }
+        else { F.tile_cost = d_cost; r->order_state = 1; }
     } else if (r->order_state == 1) {
         use = 0;
     }
@@ -767,45 +661,14 @@ int tile_order_step(rt_renderer *r, FrameArgs &F, bool split_ok, FramePlan &P) {
         // frame and the order write after every frame still reading the previous order,
         // whatever streams the caller used
         HIP_TRY(hipDeviceSynchronize());
-        std::vector<uint32_t> cost(n), ord(n);
-        HIP_TRY(hipMemcpy(cost.data(), r->d_cost + (size_t)use * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        std::vector<uint32_t> cost(n);
+        HIP_TRY(hipMemcpy(cost.data(), d_cost + (size_t)use * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         r->host_cost = cost;
-        {   // a tile's cost is its wave's residence time, so sum / slots is the frame's throughput
-            // time and the costliest tile its latency floor (mig29 x16 1080p: 3.6x, its 1/2 shard
-            // 7x; TEAPOT-F 1080p 1.2-1.3x).  A sample-split frame's map holds one chunk's cycles
-            // per tile (the last unit of the tile to finish writes it): nchunks of them run.
-            double sum = 0, mx = 0;
-            for (uint32_t c : cost) { sum += c; mx = std::max<double>(mx, c); }
-            const double slots = (double)r->scene->num_cus * 4.0 * 7.0;
-            r->tail_bound = sum > 0 && mx * slots > 2.0 * sum * std::max(1u, F.nchunks);
-        }
-        for (uint32_t i = 0; i < n; ++i) ord[i] = i;
-        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-
-        // The costliest tiles can bound the frame's tail (one wave's latency chain): the split
-        // order runs the first k of them as two waves of half a tile each (entry bit 31 =
-        // split, bit 30 = which half).  It shortens tail-bound frames (mig29 x16 -10 %, 720p
-        // TEAPOT-F -9 %) and lengthens throughput-bound ones (1080p TEAPOT-F +9 %: the half-
-        // empty waves cost issue slots), so with RT_SPLIT_HEAVY = -1 (default) both orders are
-        // timed on two frames each and the faster one is kept; frames are identical either way.
-        uint32_t k = 0;
-        if (split_ok) {
-            const int32_t hs = r->scene->heavy_split;
-            k = std::min<uint32_t>(n, hs < 0 ? n / 32u : (uint32_t)hs);
-        }
-        // RT_SPLIT_PARTS: a split tile runs as 2 (rows 0-3 / 4-7), 4 or 8 waves of a part each
-        const uint32_t parts = r->scene->split_parts;
-        std::vector<uint32_t> ent(ord), sp;
-        for (uint32_t i = 0; i < k; ++i)
-            for (uint32_t q = 0; q < parts; ++q) sp.push_back(ord[i] | 0x80000000u | (q << 28));
-        for (uint32_t i = k; i < n; ++i) sp.push_back(ord[i]);
-        if (r->scene->xcd_order && split_ok) {   // both orders grouped by XCD (global-node frame kernel)
-            const uint32_t *map = F.tile_map ? r->map_host.data() : nullptr;
-            ent = xcd_grouped_order(F, map, ord, cost, parts);
-            sp = xcd_grouped_order(F, map, sp, cost, parts);
-        }
-        ent.insert(ent.end(), sp.begin(), sp.end());
-        HIP_TRY(hipMemcpy(r->d_order, ent.data(), ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        r->tail_bound = tail_bound(cost, r->scene->num_cus, F.nchunks);
+        const uint32_t k = split_count(n, r->scene->heavy_split, split_ok), parts = r->scene->split_parts;
+        const TileWhere where{F.tiles_x, F.shard, F.nshards, F.tile_map ? r->map_host.data() : nullptr};
+        const std::vector<uint32_t> ent = build_tile_order(cost, k, parts, r->scene->xcd_order && split_ok, where);
+        HIP_TRY(hipMemcpy(d_order, ent.data(), ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         r->order_split = k;
         r->order_parts = parts;
         r->order_state = 2;
@@ -823,9 +686,9 @@ int tile_order_step(rt_renderer *r, FrameArgs &F, bool split_ok, FramePlan &P) {
             r->use_split = tuned_alternative(r->split_ms);
         }
         const bool split = P.split.group >= 0 ? alternative_group(P.split) : r->use_split;
-        F.order = split ? r->d_order + n : r->d_order;
-        F.nunits = F.ntiles_local * F.nchunks + (split ? r->order_split * (r->order_parts - 1u) : 0u);   // split only with nchunks 1
-        F.part_shift = r->order_parts == 8 ? 3u : r->order_parts == 4 ? 4u : 5u;
+        F.order = split ? d_order + n : d_order;
+        F.nunits = order_units(F.ntiles_local, F.nchunks, split, r->order_split, r->order_parts);
+        F.part_shift = part_shift(r->order_parts);
     }
     return RT_OK;
 }
@@ -888,14 +751,14 @@ int frame_args(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
     F.rw = 1.0f / (float)r->W;   // Camera::rWidth / rHeight (camera.h:98-99)
     F.rh = 1.0f / (float)r->H;
     F.W = r->W; F.H = r->H; F.spp = p->spp; F.depth = p->depth; F.frame = p->frame; F.reset = p->reset ? 1 : 0;
-    const uint32_t tiles_x = (r->W + 7) / 8, tiles_y = (r->H + 7) / 8, ntiles = tiles_x * tiles_y;
-    F.shard = shard; F.nshards = nshards; F.tiles_x = tiles_x;
-    F.ntiles_local = shard < ntiles ? (ntiles - shard + nshards - 1) / nshards : 0;
+    const TileGrid g = r->grid();
+    F.shard = shard; F.nshards = nshards; F.tiles_x = g.tiles_x;
+    F.ntiles_local = local_tiles(g.ntiles, shard, nshards);
     if (tiles) {   // an explicit deal (rt_render_shard_tiles)
-        int rc = set_tile_map(r, tiles, ntiles_map, ntiles);
+        int rc = set_tile_map(r, tiles, ntiles_map, g.ntiles);
         if (rc != RT_OK) return rc;
         F.ntiles_local = ntiles_map;
-        F.tile_map = r->d_map;
+        F.tile_map = r->d_map.as<uint32_t>();
     }
     F.acc = r->d_acc;
     F.counters = r->d_counters;
@@ -925,57 +788,30 @@ int work_frame(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, u
     work.assign(n, 0u);
     if (n == 0) return RT_OK;
     rt_scene *s = r->scene;
-    if (n > r->work_cap) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (r->d_work) HIP_TRY(hipFree(r->d_work));
-        r->d_work = nullptr;
-        r->work_cap = 0;
-        HIP_TRY(hipMalloc(&r->d_work, sizeof(uint32_t) * n));
-        r->work_cap = n;
-    }
+    if ((rc = r->d_work.grow(sizeof(uint32_t) * n, Wait::kDevice)) != RT_OK) return rc;
+    uint32_t *const d_work = r->d_work.as<uint32_t>();
     if ((rc = after_updates(s, st)) != RT_OK) return rc;
-    HIP_TRY(hipMemsetAsync(r->d_work, 0, sizeof(uint32_t) * n, st));
+    HIP_TRY(hipMemsetAsync(d_work, 0, sizeof(uint32_t) * n, st));
     SceneView view = s->view;
     view.wave_primary = 0;
     view.walk_check = RT_WALK_CHECK_OFF;
     view.walk_stats = nullptr;
     const FrameLaunch L{work_variant(p->depth, !s->view.sky_const), dim3((n + 3) / 4), stack_bytes(s), st};
-    launchers(s).work(view, F, L, r->d_work, pixel_work);
+    launchers(s).work(view, F, L, d_work, pixel_work);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(work.data(), r->d_work, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(work.data(), d_work, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
 }
 
-// Sample split: a frame (or a shard of one) with few tiles and several samples per pixel is cut
-// into (tile, sample chunk) units, so the dispatcher still balances about s->split_units waves of
-// uneven cost (a 1/8 shard at spp 8 would otherwise be one round of whole-tile waves, as long as
-// its slowest tile); the units' samples go to d_samples.
-// (first measured on TEAPOT-F shards, tools/shard_time.py: split below ~5 rounds of
-// waves, until ~10 rounds, chunks of equal sample counts.  Round 3: whole 1080p frames at
-// spp > 1 gain from it too -- CFG5-sub scene spp 16 2.41 -> 1.44 ms, mig29 x16 spp 4 1.49
-// -> 0.76 ms, TEAPOT-F spp 4 0.390 -> 0.386 ms, frames identical (profiles/r03/split_ab/) --
-// so the threshold is 40,000 tiles instead of 20,000; 80,000 measured the same or slower)
+// Sample split (sample_chunks, rt_sched.h): the frame's (tile, sample chunk) units; their samples go
+// to d_samples.
 int sample_split(rt_renderer *r, uint32_t spp, bool eligible, FrameArgs &F) {
-    const rt_scene *s = r->scene;
-    F.nchunks = 1;
-    if (eligible && spp > 1 && F.ntiles_local < s->split_units)
-        while (F.ntiles_local * F.nchunks < 2u * s->split_units && F.nchunks < spp) {
-            uint32_t d = F.nchunks + 1;                  // next divisor of spp: equal chunks
-            while (spp % d) ++d;
-            F.nchunks = d;
-        }
+    F.nchunks = sample_chunks(spp, F.ntiles_local, r->scene->split_units, eligible);
     F.nunits = F.ntiles_local * F.nchunks;
     if (F.nchunks > 1) {
-        const size_t need = sizeof(float4) * (size_t)spp * F.ntiles_local * 64u;
-        if (need > r->samples_bytes) {
-            if (r->d_samples) HIP_TRY(hipFree(r->d_samples));
-            r->d_samples = nullptr;
-            r->samples_bytes = 0;
-            HIP_TRY(hipMalloc(&r->d_samples, need));
-            r->samples_bytes = need;
-        }
-        F.samples = static_cast<float4 *>(r->d_samples);
+        if (int rc = r->d_samples.grow(sizeof(float4) * (size_t)spp * F.ntiles_local * 64u); rc != RT_OK) return rc;
+        F.samples = r->d_samples.as<float4>();
     }
     return RT_OK;
 }
@@ -993,14 +829,14 @@ int wavefront_frame(rt_renderer *r, const FrameArgs &F, const rt_camera *cam, co
         if (int rc = ensure_order(r, param_key(r, F, cam, p), n); rc != RT_OK) return rc;
         if (r->order_state == 0) {
             if (!r->cost_ev) HIP_TRY(hipEventCreateWithFlags(&r->cost_ev, hipEventDisableTiming | hipEventReleaseToDevice));
-            HIP_TRY(hipMemsetAsync(r->d_cost, 0, n * sizeof(uint32_t), st));
+            rec_cost = r->d_cost.as<uint32_t>();
+            HIP_TRY(hipMemsetAsync(rec_cost, 0, n * sizeof(uint32_t), st));
             HIP_TRY(hipEventRecord(r->cost_ev, st));
-            rec_cost = r->d_cost;
             r->order_state = 1;
         } else if (r->order_state == 1) {
             HIP_TRY(hipDeviceSynchronize());                                 // the recording frame is done
             r->host_cost.resize(n);
-            HIP_TRY(hipMemcpy(r->host_cost.data(), r->d_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(r->host_cost.data(), r->d_cost.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
             r->order_state = 3;                                              // costs held, no order
         }
     }
@@ -1086,12 +922,7 @@ int overlap_step(rt_renderer *r, FrameArgs &F, FrameLaunch &L, bool ps_ok, uint6
             // every timed frame's finishing pass preceded the last event: no buffer is in use, and
             // the ones the chosen depth never touches are released (a 1080p spp-1 buffer is 33 MB)
             const uint32_t keep = r->ps_use == 0 ? 0u : (s->ps_buffers ? s->ps_buffers : r->ps_use + 1u);
-            for (uint32_t b = keep; b <= (uint32_t)kPsMaxDepth; ++b) {
-                if (r->ps_res[b]) HIP_TRY(hipFree(r->ps_res[b]));
-                r->ps_res[b] = nullptr;
-                r->ps_res_bytes[b] = 0;
-                r->ps_fin_set[b] = false;
-            }
+            if (int rc = r->ps_res.drop_from((int)keep); rc != RT_OK) return rc;
         }
         o.depth = o.ps.group >= 0 ? overlap_depths(r->ps_tg.groups)[o.ps.group] : (uint32_t)r->ps_use;
         if (o.ps.group >= 0) r->ps_last = r->frames;
@@ -1107,7 +938,7 @@ int overlap_step(rt_renderer *r, FrameArgs &F, FrameLaunch &L, bool ps_ok, uint6
         ++r->ps_count;
         if (int rc = ensure_ps_res(r, o.buf, ps_bytes); rc != RT_OK) return rc;
         L.stream = r->pt_stream[o.lane];
-        if (r->ps_fin_set[o.buf]) HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_fin[o.buf], 0));
+        if (r->ps_res.fin_set[o.buf]) HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_res.fin[o.buf], 0));
         const bool timed_from = o.ps.group >= 0 && o.ps.index == r->ps_tg.skip;   // records the group's start event
         if (!r->ps_prev || timed_from) {
             // switching from serial frames: start behind the caller's stream; the frame a group is
@@ -1120,7 +951,7 @@ int overlap_step(rt_renderer *r, FrameArgs &F, FrameLaunch &L, bool ps_ok, uint6
             else
                 HIP_TRY(hipStreamWaitEvent(L.stream, r->ps_join, 0));
         }
-        F.samples = r->ps_res[o.buf];
+        F.samples = r->ps_res.at((int)o.buf);
     }
     if (ps_ok) r->ps_prev = o.depth;
     return RT_OK;
@@ -1148,8 +979,8 @@ int submit_frame(rt_renderer *r, const SceneView &view, const FrameArgs &F, cons
         launchers(s).pt_finish(F, P, true, st);
         HIP_TRY(hipGetLastError());
         if (o.depth > 0) {
-            HIP_TRY(hipEventRecord(r->ps_fin[o.buf], st));
-            r->ps_fin_set[o.buf] = true;
+            HIP_TRY(hipEventRecord(r->ps_res.fin[o.buf], st));
+            r->ps_res.fin_set[o.buf] = true;
         }
     }
     if (o.ps.ev_after >= 0) HIP_TRY(hipEventRecord(r->tune_ev[kOverlap][o.ps.ev_after], st));
@@ -1170,7 +1001,6 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     rt_scene *s = r->scene;
     FrameArgs F;
     if (int rc = frame_args(r, cam, p, shard, nshards, tiles, ntiles_map, F); rc != RT_OK) return rc;
-    const uint32_t tiles_x = F.tiles_x, ntiles = tiles_x * ((r->H + 7) / 8);
     if (tiles) {   // (copied only when the map changed: frames of one deal keep the same list)
         if (r->held_kind != 3 || r->held_gen != r->map_gen) {
             r->held_list = r->map_host;
@@ -1199,7 +1029,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
         F.depth = s->bvh.depth;
         kcore::launch_heat(s->view, F, stack_bytes(s), st);
         HIP_TRY(hipGetLastError());
-        r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
+        r->primary += frame_pixels(r, F) * p->spp;
         r->frames += 1;
         return RT_OK;
     }
@@ -1209,7 +1039,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     if (int rc = sample_split(r, p->spp, mode != RT_MODE_PACKET && !wavefront, F); rc != RT_OK) return rc;
     if (wavefront) {
         if (int rc = wavefront_frame(r, F, cam, p, st); rc != RT_OK) return rc;
-        r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
+        r->primary += frame_pixels(r, F) * p->spp;
         r->frames += 1;
         return RT_OK;
     }
@@ -1242,7 +1072,7 @@ int launch_render(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p
     L.v = frame_variant({mode, p->depth, !view.sky_const, s->frame_waves, F.nchunks, F.spp, F.nunits, s->num_cus,
                          P.depth > 0, view.wave_primary, view.walk_check});
     if (int rc = submit_frame(r, view, F, L, P, st); rc != RT_OK) return rc;
-    r->primary += frame_pixels(r, F, shard, nshards, tiles_x, ntiles) * p->spp;
+    r->primary += frame_pixels(r, F) * p->spp;
     r->frames += 1;
     return RT_OK;
 }
@@ -1386,7 +1216,7 @@ static int acc_tiles(rt_renderer *r, const uint32_t *d_tiles, uint32_t n, void *
     if (!r || (n && (!d_tiles || !buf))) return fail(RT_ERR_INVALID, "null argument");
     if (n == 0) return RT_OK;
     HIP_TRY(hipSetDevice(r->scene->device));
-    const uint32_t tiles_x = (r->W + 7) / 8;
+    const uint32_t tiles_x = r->grid().tiles_x;
     hipLaunchKernelGGL(k_acc_tiles, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, r->d_acc,
                        static_cast<float4 *>(buf), d_tiles, n, tiles_x, r->W, r->H, unpack);
     HIP_TRY(hipGetLastError());
@@ -1420,21 +1250,7 @@ int rt::render_work(rt_renderer *r, const rt_camera *cam, const rt_frame_params 
 }
 
 bool rt::renderer_held_tiles(const rt_renderer *r, std::vector<uint32_t> &tiles) {
-    tiles.clear();
-    const uint32_t ntiles = ((r->W + 7) / 8) * ((r->H + 7) / 8);
-    switch (r->held_kind) {
-    case 1:
-        for (uint32_t t = 0; t < ntiles; ++t) tiles.push_back(t);
-        return true;
-    case 2:
-        for (uint32_t t = r->held_shard; t < ntiles; t += r->held_nshards) tiles.push_back(t);
-        return true;
-    case 3:
-        tiles = r->held_list;
-        return true;
-    default:
-        return false;
-    }
+    return held_tiles(r->held_kind, r->grid().ntiles, r->held_shard, r->held_nshards, r->held_list, tiles);
 }
 
 int rt::renderer_geometry(const rt_renderer *r, uint32_t *W, uint32_t *H, int *device) {
@@ -1682,33 +1498,21 @@ int rt_renderer_destroy(rt_renderer *r) {
     (void)hipFree(r->d_acc);
     (void)hipFree(r->d_counters);
     if (r->d_rgb) (void)hipFree(r->d_rgb);
-    for (int k = 0; k < kPtMaxSlots; ++k)
-        if (r->d_pt[k]) (void)hipFree(r->d_pt[k]);
+    if (r->d_sum) (void)hipFree(r->d_sum);
+    each_buffer(*r, [](DevBuf &b) { (void)b.release(); });
     for (int k = 0; k < kPsMaxDepth; ++k) {
         if (r->pt_stream[k]) (void)hipStreamDestroy(r->pt_stream[k]);
         if (r->pt_lv[k]) (void)hipEventDestroy(r->pt_lv[k]);
     }
-    for (int k = 0; k <= kPtMaxSlots; ++k) {
-        if (r->d_res[k]) (void)hipFree(r->d_res[k]);
-        if (r->pt_fin[k]) (void)hipEventDestroy(r->pt_fin[k]);
-    }
-    if (r->d_sum) (void)hipFree(r->d_sum);
-    if (r->d_samples) (void)hipFree(r->d_samples);
-    if (r->d_order) (void)hipFree(r->d_order);
-    if (r->d_cost) (void)hipFree(r->d_cost);
-    if (r->d_map) (void)hipFree(r->d_map);
-    if (r->d_work) (void)hipFree(r->d_work);
-    if (r->d_where) (void)hipFree(r->d_where);
     for (auto &row : r->tune_ev)
         for (auto &e : row)
             if (e) (void)hipEventDestroy(e);
-    if (r->ps_join) (void)hipEventDestroy(r->ps_join);
-    if (r->cost_ev) (void)hipEventDestroy(r->cost_ev);
-    if (r->stall_ev) (void)hipEventDestroy(r->stall_ev);
-    for (int b = 0; b < kPsMaxDepth + 1; ++b) {
-        if (r->ps_res[b]) (void)hipFree(r->ps_res[b]);
-        if (r->ps_fin[b]) (void)hipEventDestroy(r->ps_fin[b]);
-    }
+    for (hipEvent_t e : r->pt_res.fin)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : r->ps_res.fin)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {r->ps_join, r->cost_ev, r->stall_ev})
+        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(r->stream);
     delete r;
     return RT_OK;
@@ -1786,8 +1590,7 @@ int rt_renderer_gbuffer_walk(const rt_renderer *r, int pixels, int *wave_walk, u
 
 int rt_shard_capacity(uint32_t W, uint32_t H, uint32_t nshards, uint32_t *pixels) {
     if (!pixels || !nshards || !W || !H) return fail(RT_ERR_INVALID, "rt_shard_capacity: bad argument");
-    uint32_t ntiles = ((W + 7) / 8) * ((H + 7) / 8);
-    *pixels = ((ntiles + nshards - 1) / nshards) * 64u;
+    *pixels = local_tiles(tile_grid(W, H).ntiles, 0, nshards) * 64u;   // shard 0's count: no shard has more
     return RT_OK;
 }
 
@@ -1801,9 +1604,9 @@ int rt_assemble_shards(rt_renderer *r, const uint32_t *gathered, uint32_t nshard
     HIP_TRY(hipSetDevice(r->scene->device));
     uint32_t cap = 0;
     rt_shard_capacity(r->W, r->H, nshards, &cap);
-    uint32_t tiles_x = (r->W + 7) / 8, ntiles = tiles_x * ((r->H + 7) / 8);
+    const TileGrid g = r->grid();
     hipStream_t st = (hipStream_t)stream;
-    launch_assemble(gathered, cap, nshards, nullptr, tiles_x, ntiles, r->W, r->H, rgb8, st);
+    launch_assemble(gathered, cap, nshards, nullptr, g.tiles_x, g.ntiles, r->W, r->H, rgb8, st);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -1819,10 +1622,10 @@ int rt_assemble_tiles(rt_renderer *r, const uint32_t *gathered, uint32_t stride_
     if (!r || !gathered || !deal_tiles || !deal_off || !rgb8 || !nshards || nshards > 255)
         return fail(RT_ERR_INVALID, "rt_assemble_tiles: bad argument");
     HIP_TRY(hipSetDevice(r->scene->device));
-    const uint32_t tiles_x = (r->W + 7) / 8, ntiles = tiles_x * ((r->H + 7) / 8);
+    const uint32_t tiles_x = r->grid().tiles_x, ntiles = r->grid().ntiles;
     if (deal_off[0] != 0 || deal_off[nshards] != ntiles) return fail(RT_ERR_INVALID, "rt_assemble_tiles: the deal must cover every tile once");
     uint64_t h = fnv1a(deal_off, sizeof(uint32_t) * (nshards + 1u), fnv1a(deal_tiles, sizeof(uint32_t) * ntiles));
-    if (!r->d_where || h != r->where_hash) {
+    if (!r->d_where.p || h != r->where_hash) {
         std::vector<uint32_t> where(ntiles, 0xffffffffu);
         for (uint32_t k = 0; k < nshards; ++k) {
             if (deal_off[k + 1] < deal_off[k] || (size_t)(deal_off[k + 1] - deal_off[k]) * 64u > stride_px)
@@ -1834,16 +1637,11 @@ int rt_assemble_tiles(rt_renderer *r, const uint32_t *gathered, uint32_t stride_
             }
         }
         HIP_TRY(hipDeviceSynchronize());   // an assembly may still read the previous map
-        if (!r->d_where || r->where_cap < ntiles) {
-            if (r->d_where) HIP_TRY(hipFree(r->d_where));
-            r->d_where = nullptr;
-            HIP_TRY(hipMalloc(&r->d_where, sizeof(uint32_t) * ntiles));
-            r->where_cap = ntiles;
-        }
-        HIP_TRY(hipMemcpy(r->d_where, where.data(), sizeof(uint32_t) * ntiles, hipMemcpyHostToDevice));
+        if (int rc = r->d_where.grow(sizeof(uint32_t) * ntiles); rc != RT_OK) return rc;
+        HIP_TRY(hipMemcpy(r->d_where.p, where.data(), sizeof(uint32_t) * ntiles, hipMemcpyHostToDevice));
         r->where_hash = h;
     }
-    launch_assemble(gathered, stride_px, nshards, r->d_where, tiles_x, ntiles, r->W, r->H, rgb8, (hipStream_t)stream);
+    launch_assemble(gathered, stride_px, nshards, r->d_where.as<uint32_t>(), tiles_x, ntiles, r->W, r->H, rgb8, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -1929,21 +1727,15 @@ int rt_renderer_overlap_depth(const rt_renderer *r, int *depth, float ms[8]) {
 
 int rt_renderer_device_bytes(const rt_renderer *r, uint64_t *bytes, uint32_t *ps_buffers) {
     if (!r || !bytes) return fail(RT_ERR_INVALID, "rt_renderer_device_bytes: null argument");
+    // what is allocated: the fixed blocks (accumulator, counters; the staging frame and the running
+    // sample sum once a call needed them) and every growable buffer
     const uint64_t pix = (uint64_t)r->W * r->H;
-    const uint64_t tiles = (uint64_t)((r->W + 7) / 8) * ((r->H + 7) / 8);
-    uint64_t b = 16u * pix + kCounterSlots * 8u * sizeof(unsigned long long);   // accumulator, counters
+    uint64_t b = 16u * pix + kCounterSlots * 8u * sizeof(unsigned long long);
     if (r->d_rgb) b += 4u * pix;
-    for (size_t k : r->pt_bytes) b += k;
-    for (size_t k : r->res_bytes) b += k;
-    if (r->d_sum) b += tiles * 64u * sizeof(float4);
-    b += r->samples_bytes;
-    b += 5u * (uint64_t)r->order_n * sizeof(uint32_t);   // plain + split order, two cost maps
-    b += (r->d_map ? r->map_cap : 0) * sizeof(uint32_t) + (r->d_where ? r->where_cap : 0) * sizeof(uint32_t);
+    if (r->d_sum) b += sum_bytes(r);
+    each_buffer(*r, [&](const DevBuf &x) { b += x.bytes; });
     uint32_t nps = 0;
-    for (int k = 0; k <= kPsMaxDepth; ++k) {
-        b += r->ps_res_bytes[k];
-        nps += r->ps_res[k] != nullptr;
-    }
+    for (const DevBuf &x : r->ps_res.buf) nps += x.p != nullptr;
     *bytes = b;
     if (ps_buffers) *ps_buffers = nps;
     return RT_OK;
@@ -1952,8 +1744,7 @@ int rt_renderer_device_bytes(const rt_renderer *r, uint64_t *bytes, uint32_t *ps
 int rt_renderer_tile_work(rt_renderer *r, const rt_camera *cam, const rt_frame_params *p, uint32_t *work, uint32_t n,
                           uint32_t *pixel_work_dev, void *stream) {
     if (!r || !cam || !p || (n && !work)) return fail(RT_ERR_INVALID, "rt_renderer_tile_work: null argument");
-    const uint32_t ntiles = ((r->W + 7) / 8) * ((r->H + 7) / 8);
-    if (n < ntiles) return fail(RT_ERR_INVALID, "rt_renderer_tile_work: room for every tile needed");
+    if (n < r->grid().ntiles) return fail(RT_ERR_INVALID, "rt_renderer_tile_work: room for every tile needed");
     std::vector<uint32_t> w;
     int rc = work_frame(r, cam, p, 0, 1, nullptr, 0, w, pixel_work_dev, (hipStream_t)stream);
     if (rc != RT_OK) return rc;

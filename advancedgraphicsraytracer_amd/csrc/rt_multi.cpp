@@ -26,6 +26,7 @@
 
 #include "rt_dev_types.h"
 #include "rt_internal.h"
+#include "rt_sched.h"
 
 using namespace rt;
 
@@ -276,7 +277,7 @@ int bind_renderer(rt_comm *c, rt_renderer *r) {
     if (c->renderer == r && c->W == W && c->H == H) return RT_OK;
     if (c->pending >= 0) return fail(RT_ERR_INVALID, "rt_render_frame_multi: flush the pipelined frame before switching renderers");
     free_buffers(c);
-    const uint32_t ntiles = ((W + 7) / 8) * ((H + 7) / 8);
+    const uint32_t ntiles = tile_grid(W, H).ntiles;
     // every deal fits: a shard holds at most all tiles (a balanced deal's region may hold many cheap ones)
     const uint32_t stride = ntiles * 64u;
     for (int k = 0; k < 2; ++k) {
@@ -351,7 +352,7 @@ unsigned sync_event_flags() {
 // deal that slot was rendered with (rank 0's own tiles are already there)
 int scatter_peers(rt_comm *c, int k, uint32_t *out, hipStream_t st) {
     const Deal &d = *c->slot_deal[k];
-    launch_assemble(c->gathered[k], c->stride, (uint32_t)c->world, d.id ? d.d_where : nullptr, (c->W + 7) / 8,
+    launch_assemble(c->gathered[k], c->stride, (uint32_t)c->world, d.id ? d.d_where : nullptr, tile_grid(c->W, c->H).tiles_x,
                     c->ntiles, c->W, c->H, out, st, 1u);
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -626,7 +627,7 @@ int rt_tile_deal(uint32_t width, uint32_t height, const uint32_t *cost, uint32_t
                  uint32_t *deal_off) {
     if (!width || !height || !nshards || nshards > 255 || !deal_tiles || !deal_off)
         return fail(RT_ERR_INVALID, "rt_tile_deal: bad argument");
-    const uint32_t tx = (width + 7) / 8, ty = (height + 7) / 8, n = tx * ty;
+    const uint32_t tx = tile_grid(width, height).tiles_x, n = tile_grid(width, height).ntiles;
     auto morton = [](uint32_t x, uint32_t y) {
         uint64_t m = 0;
         for (int b = 0; b < 16; ++b) m |= (uint64_t)((x >> b) & 1u) << (2 * b) | (uint64_t)((y >> b) & 1u) << (2 * b + 1);

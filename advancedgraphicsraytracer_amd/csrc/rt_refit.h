@@ -24,6 +24,34 @@
 
 namespace rt {
 
+// An owned, growable device buffer: the one text that frees and allocates.  grow() leaves a buffer of
+// at least `need` bytes (the old block is freed, its contents are not kept) and says what has to
+// finish before the old block goes: nothing (hipFree itself), the stream that used it, or every
+// stream of the device.  A buffer that is large enough costs one comparison.
+enum class Wait { kNone, kStream, kDevice };
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+
+    template <class T>
+    T *as() const { return static_cast<T *>(p); }
+    int release() {
+        if (p) HIP_TRY(hipFree(p));
+        p = nullptr;
+        bytes = 0;
+        return RT_OK;
+    }
+    int grow(size_t need, Wait wait = Wait::kNone, hipStream_t st = nullptr) {
+        if (need <= bytes) return RT_OK;
+        if (wait == Wait::kStream) HIP_TRY(hipStreamSynchronize(st));
+        if (wait == Wait::kDevice) HIP_TRY(hipDeviceSynchronize());
+        if (int rc = release(); rc != RT_OK) return rc;
+        HIP_TRY(hipMalloc(&p, need));
+        bytes = need;
+        return RT_OK;
+    }
+};
+
 // A treelet is a whole subtree of at most this many nodes; one workgroup refits it.
 constexpr uint32_t kTreeletNodes = 256;
 
@@ -70,8 +98,8 @@ void seed_slot_boxes(const Bvh &b, const std::vector<uint8_t> &pinfo, const std:
 // last fold, which entry point it came from (update_async's `kind`).
 constexpr int kXformSlots = 8;
 struct XformSlot {
-    void *host = nullptr, *dev = nullptr;
-    size_t bytes = 0;
+    void *host = nullptr;           // pinned, as large as dev
+    DevBuf dev;
     hipEvent_t ev = nullptr;
     bool used = false;
 };
@@ -121,15 +149,13 @@ struct SceneRecords {
     float margin;   // SceneView::walk_margin
 };
 
-// a device buffer of at least `need` bytes (the old one is freed, its contents are not kept)
+// the same for a pointer and a size kept apart (the scene's staging, its range table, its type bytes)
 inline int grow(void **buf, size_t *have, size_t need) {
-    if (need <= *have) return RT_OK;
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(buf, need));
-    *have = need;
-    return RT_OK;
+    DevBuf b{*buf, *have};
+    const int rc = b.grow(need);
+    *buf = b.p;
+    *have = b.bytes;
+    return rc;
 }
 template <typename T>
 int upload(void **dst, const std::vector<T> &src) {

@@ -197,7 +197,7 @@ void free_refit(RefitState &R) {
     if (U.done) (void)hipEventDestroy(U.done);
     for (XformSlot &x : U.ring) {
         if (x.host) (void)hipHostFree(x.host);
-        if (x.dev) (void)hipFree(x.dev);
+        (void)x.dev.release();
         if (x.ev) (void)hipEventDestroy(x.ev);
     }
     U = AsyncUpdates{};
@@ -331,25 +331,22 @@ int update_xform_async(RefitState &R, const SceneRecords &S, const std::vector<u
     // returns at once unless all the slots are in flight
     if (x.used) HIP_TRY(hipEventSynchronize(x.ev));
     if (!x.ev) HIP_TRY(hipEventCreateWithFlags(&x.ev, hipEventDisableTiming));
-    if (need > x.bytes) {
+    if (need > x.dev.bytes) {
         const size_t cap = std::max<size_t>(4096, 2 * need);
+        if (int rc = x.dev.release(); rc != RT_OK) return rc;   // (first: the size that admits a table is the device twin's)
         if (x.host) HIP_TRY(hipHostFree(x.host));
         x.host = nullptr;
-        if (x.dev) HIP_TRY(hipFree(x.dev));
-        x.dev = nullptr;
-        x.bytes = 0;
         HIP_TRY(hipHostMalloc(&x.host, cap, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&x.dev, cap));
-        x.bytes = cap;
+        if (int rc = x.dev.grow(cap); rc != RT_OK) return rc;
     }
     std::memcpy(x.host, tab.data(), need);
     TriXform src{};
-    src.R.first = (const uint32_t *)x.dev;
+    src.R.first = x.dev.as<const uint32_t>();
     src.R.pre = src.R.first + nr;
     src.R.M = (const float *)(src.R.pre + nr + 1);
     src.R.nr = nr;
     src.rest = rest_dev;
-    const UpdateCopy table{x.dev, x.host, need, hipMemcpyHostToDevice};
+    const UpdateCopy table{x.dev.p, x.host, need, hipMemcpyHostToDevice};
     const uint64_t before = U.submitted;
     const int rc = update_async(R, S, src, tab[2 * (size_t)nr], st, 1, &table, 1, ticket_out);
     if (U.submitted != before) {   // enqueued (even where a later step failed): the slot is taken
